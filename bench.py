@@ -13,7 +13,11 @@ scripts/test.py:1059-1084); the only collective is the RCCL all-gather of the fi
 the timed region.  Weights are random-init tensors of the Kubric architecture (the 61 zero-init
 tensors re-drawn so the network is not identically 0), inputs synthetic and resident in HBM.
 
-Prints ONE JSON line on rank 0 (see the driver contract), including
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times --steps steps and
+prints metric / value (steps/s) / unit / higher_is_better / dtype / ms_per_step (one timed step) with the workload's
+configuration; --dump-outputs DIR also writes the final latents of the last timed step (DIR/latents.npy, fp32; the
+inputs are seeded, so two builds can be compared output for output).  `--full` adds a spread over --repeats timed
+regions and
   roofline      dominant kernel family (gemm_p8_kernel / gemm_pp_kernel / gemm_f16_kernel, the MFMA implicit GEMMs): algorithmic
                 FLOPs of all its launches in one step / the sum of their durations, measured with
                 HIP events on the launch stream in an instrumented eager step right after the timed
@@ -437,15 +441,32 @@ def main():
     ap.add_argument("--backend", default="nccl",
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only to exercise "
                          "the multi-rank path on a box with fewer GPUs than ranks, with GCD_BENCH_SHARE_GPU=1)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps steps each: the first is the reported one (driver "
-                         "contract), all of them feed timing_stats (median)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: further timed regions (--repeats), the instrumented "
+                         "per-kernel step (roofline, attention), the CPU baseline and the parity check against the "
+                         "oracle, the rank checks of N > 1; without it a run sets up, warms up, times --steps steps "
+                         "and prints the result line")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="(--full; default 5) timed regions of --steps steps each: the first is the reported one "
+                         "(driver contract), all of them feed timing_stats (median)")
     ap.add_argument("--dump-profile", type=str, default=None,
-                    help="write the per-launch HIP-event table of the instrumented step (JSON)")
+                    help="(--full) write the per-launch HIP-event table of the instrumented step (JSON)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the final latents a caller receives, gathered "
+                         "over ranks) as DIR/latents.npy in float32")
     ap.add_argument("--train", action="store_true",
                     help="instead of the sampler step: BASELINE.json cfg4's fine-tune step on one GPU, bf16 and fp16 "
                          "operands, with its parity against the reference's fp32 autograd golden (one JSON line)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and not args.train:
+        for flag, given in (("--repeats", args.repeats not in (None, 1)), ("--dump-profile", args.dump_profile),
+                            ("--cpu-baseline-full", args.cpu_baseline_full)):
+            if given:
+                ap.error(f"{flag} is part of the --full run")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     if args.train:
@@ -459,7 +480,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
                str(Path(__file__).resolve())] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        import subprocess
+        sys.exit(subprocess.call(cmd))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -514,7 +536,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    full = args.full
+    if full:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with loop:
         # warm-up: >= 2 steps so that the eager step and the graph capture are outside the timing
         nwarm = max(args.warmup, 2 if sampler.use_graph else 1)
@@ -522,43 +546,49 @@ def main():
             loop.step(i)
         barrier()
         t0 = time.perf_counter()
-        e0.record(loop.side)
+        if full:
+            e0.record(loop.side)
         for i in range(args.steps):
             loop.step(nwarm + i)
-        e1.record(loop.side)
+        if full:
+            e1.record(loop.side)
         barrier()
         wall = time.perf_counter() - t0
-        ev_ms = e0.elapsed_time(e1)
-        finite = bool(torch.isfinite(loop.x).all())
-        # further regions of the same length: spread of the measurement (the first one is `value`)
+        # what the timed path computed in its last step, kept before the --full legs below move loop.x
+        x_last = loop.x.clone() if full else loop.x
         regions = [wall]
-        for r in range(1, max(1, args.repeats)):
-            barrier()
-            t1 = time.perf_counter()
-            for i in range(args.steps):
-                loop.step(nwarm + r * args.steps + i)
-            barrier()
-            regions.append(time.perf_counter() - t1)
+        if full:
+            ev_ms = e0.elapsed_time(e1)
+            finite = bool(torch.isfinite(x_last).all())
+            # further regions of the same length: spread of the measurement (the first one is `value`)
+            for r in range(1, max(1, args.repeats)):
+                barrier()
+                t1 = time.perf_counter()
+                for i in range(args.steps):
+                    loop.step(nwarm + r * args.steps + i)
+                barrier()
+                regions.append(time.perf_counter() - t1)
 
-        # ---- instrumented eager step: per-launch HIP events on the launch stream ----
-        prof = ops.start_profile()
-        loop.sig.copy_(loop.sigmas[0:2])
-        loop.launch_step()
-        loop.side.synchronize()
-        ops.stop_profile()
+            # ---- instrumented eager step: per-launch HIP events on the launch stream ----
+            prof = ops.start_profile()
+            loop.sig.copy_(loop.sigmas[0:2])
+            loop.launch_step()
+            loop.side.synchronize()
+            ops.stop_profile()
     kinds = {}
     table = []
-    import ctypes as C
-    for r in prof:
-        ms = C.c_float()
-        _lib.check(lib.gcd_event_elapsed_ms(r["start"], r["stop"], C.byref(ms)))
-        k = kinds.setdefault(r["kind"], dict(flops=0.0, ms=0.0, launches=0))
-        k["flops"] += r["flops"]
-        k["ms"] += ms.value
-        k["launches"] += 1
-        table.append({kk: vv for kk, vv in r.items() if kk not in ("start", "stop")} | {"ms": ms.value})
-        lib.gcd_event_destroy(r["start"])
-        lib.gcd_event_destroy(r["stop"])
+    if full:
+        import ctypes as C
+        for r in prof:
+            ms = C.c_float()
+            _lib.check(lib.gcd_event_elapsed_ms(r["start"], r["stop"], C.byref(ms)))
+            k = kinds.setdefault(r["kind"], dict(flops=0.0, ms=0.0, launches=0))
+            k["flops"] += r["flops"]
+            k["ms"] += ms.value
+            k["launches"] += 1
+            table.append({kk: vv for kk, vv in r.items() if kk not in ("start", "stop")} | {"ms": ms.value})
+            lib.gcd_event_destroy(r["start"])
+            lib.gcd_event_destroy(r["stop"])
     loop.close()
     if args.dump_profile and rank == 0:
         Path(args.dump_profile).parent.mkdir(parents=True, exist_ok=True)
@@ -568,32 +598,36 @@ def main():
     elapsed = torch.tensor(regions, device=dev, dtype=torch.float64)
     per_rank = [elapsed.clone()]
     if dist is not None:
-        per_rank = [torch.empty_like(elapsed) for _ in range(world)]
-        dist.all_gather(per_rank, elapsed)
+        if full:
+            per_rank = [torch.empty_like(elapsed) for _ in range(world)]
+            dist.all_gather(per_rank, elapsed)
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     # how many ranks RCCL actually connected: a sum of ones over the nccl (= RCCL) backend, executed, not inferred
     rccl_ranks = 0
-    if dist is not None and args.backend == "nccl":
+    if full and dist is not None and args.backend == "nccl":
         one = torch.ones(1, device=dev)
         dist.all_reduce(one)
         rccl_ranks = int(one.item())
         if dist.get_backend() != "nccl" or rccl_ranks != args.gpus:
             raise SystemExit(f"bench.py: {rccl_ranks} ranks answered over '{dist.get_backend()}' for --gpus {args.gpus}")
     t_gather0 = time.perf_counter()
-    gathered = gather_clips(loop.x, dist)             # the one collective of the path
+    gathered = gather_clips(x_last, dist)             # the one collective of the path
     torch.cuda.synchronize(dev)
     gather_ms = (time.perf_counter() - t_gather0) * 1e3
     elapsed_s = float(elapsed[0].item())
     region_ms = sorted(float(v) * 1e3 / args.steps for v in elapsed.tolist())
 
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        d = Path(args.dump_outputs)
+        d.mkdir(parents=True, exist_ok=True)
+        # [world, 14, 4, h, w] fp32: 2 MiB per rank at 72x128
+        np.save(d / "latents.npy", gathered.detach().float().cpu().numpy())
+
     if rank == 0:
         ms_per_step = elapsed_s * 1e3 / args.steps
         steps_per_s = world * args.steps / elapsed_s
         step_tf = STEP_TFLOP.get((h, w))
-        gk = kinds.get("gemm", dict(flops=0.0, ms=1.0, launches=0))
-        ak = kinds.get("attn_spatial", dict(flops=0.0, ms=1.0, launches=0))
-        gemm_tflops = gk["flops"] / (gk["ms"] * 1e-3) / 1e12
-        traffic, traffic_note = _pmc_traffic()
         out = {
             "metric": "UNet denoise steps/sec, 14-frame 576x1024 SVD latents",
             "value": round(steps_per_s, 4), "unit": "steps/s", "n_gpus": world, "steps": args.steps,
@@ -606,42 +640,15 @@ def main():
                        "parallelism": f"replica per GPU x{world}, RCCL all-gather of final latents",
                        "precision": "fp16 MFMA operands, fp32 accumulate / residual stream / softmax / norms",
                        "graph": sampler.use_graph},
-            "roofline": {"bound": "mfma", "achieved": round(gemm_tflops, 2), "peak": PEAK_MFMA_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(gemm_tflops / PEAK_MFMA_TFLOPS, 4),
-                         "traffic": traffic, "traffic_unit": "bytes per launch (fabric-side: HBM + Infinity Cache)",
-                         "traffic_profile": traffic_note, "sources_digest": sources_digest(),
-                         "kernel": "gemm_p8_kernel (+ gemm_pp_kernel, gemm_f16_kernel for the shapes it does not take; ff_fused_kernel = LayerNorm + FeedForward and lnqkv_kernel = LayerNorm + q|k|v at C = 320, conv3x3_narrow_kernel = the output head; MFMA implicit-GEMM family: Linear, Conv2d 3x3/1x1, Conv3d (3,1,1))",
-                         "launches_per_step": gk["launches"],
-                         "algorithmic_tflop_per_step": round(gk["flops"] / 1e12, 3),
-                         "kernel_ms_per_step": round(gk["ms"], 3)},
-            "attention": {"kernel": "attn_spatial64p_kernel (72x128, 36x64 tokens) + attn_spatial_kernel", "achieved": round(
-                ak["flops"] / (ak["ms"] * 1e-3) / 1e12, 2), "unit": "TFLOP/s",
-                "algorithmic_tflop_per_step": round(ak["flops"] / 1e12, 3),
-                "kernel_ms_per_step": round(ak["ms"], 3), "launches_per_step": ak["launches"]},
             "frame_evals_per_s": round(steps_per_s * 2 * T, 2),
-            "hip_event_ms_per_step_rank0": round(ev_ms / args.steps, 3),
-            "timing_stats": {"regions": len(region_ms), "steps_per_region": args.steps,
-                             "ms_per_step_sorted": [round(v, 3) for v in region_ms],
-                             "ms_per_step_median": round(region_ms[len(region_ms) // 2], 3),
-                             "reported_region": "first (max over ranks)"},
-            "per_rank_ms_per_step": [round(float(t[0]) * 1e3 / args.steps, 3) for t in per_rank],
-            "rccl_ranks": rccl_ranks,
-            "dist_backend": args.backend if dist is not None else None,
-            "gather_ms": round(gather_ms, 3), "gathered_shape": list(gathered.shape),
-            "output_finite": finite,
-            "workspace_gib": round(net.engine.ws.nbytes() / 2 ** 30, 2),
         }
         if step_tf is not None:
             out["step_tflops_per_gpu"] = round(step_tf * args.steps / elapsed_s, 2)
             out["step_frac_of_mfma_peak"] = round(step_tf * args.steps / elapsed_s / PEAK_MFMA_TFLOPS, 4)
         parity_ok = True
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity(net, sampler, fd, T, dev, 5, cond,
-                                                                             full=args.cpu_baseline_full)
-            parity_ok = out["parity"]["ok"]
-        elif world > 1:
-            out["cpu_baseline_note"] = ("N > 1 lines carry no cpu_baseline / parity: both are measured by the N = 1 "
-                                        "line only (BENCH contract: rank 0 at N = 1)")
+        if full:
+            parity_ok = full_legs(out, args, kinds, ev_ms, region_ms, per_rank, rccl_ranks, dist, gather_ms,
+                                  gathered, finite, net, sampler, fd, T, dev, cond, world)
         print(json.dumps(out), flush=True)
         if not parity_ok:
             print(f"bench.py: PARITY FAILED: rel-L2 {out['parity']['rel_l2']:.3e} > {PARITY_TOL}",
@@ -650,6 +657,50 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_legs(out, args, kinds, ev_ms, region_ms, per_rank, rccl_ranks, dist, gather_ms, gathered, finite,
+              net, sampler, fd, T, dev, cond, world):
+    """`--full`: what the line carries beyond the headline figure (per-kernel roofline of the instrumented step,
+    spread over --repeats regions, the CPU baseline and the parity check).  Returns whether parity held."""
+    gk = kinds.get("gemm", dict(flops=0.0, ms=1.0, launches=0))
+    ak = kinds.get("attn_spatial", dict(flops=0.0, ms=1.0, launches=0))
+    gemm_tflops = gk["flops"] / (gk["ms"] * 1e-3) / 1e12
+    traffic, traffic_note = _pmc_traffic()
+    out.update({
+        "roofline": {"bound": "mfma", "achieved": round(gemm_tflops, 2), "peak": PEAK_MFMA_TFLOPS,
+                     "unit": "TFLOP/s", "frac": round(gemm_tflops / PEAK_MFMA_TFLOPS, 4),
+                     "traffic": traffic, "traffic_unit": "bytes per launch (fabric-side: HBM + Infinity Cache)",
+                     "traffic_profile": traffic_note, "sources_digest": sources_digest(),
+                     "kernel": "gemm_p8_kernel (+ gemm_pp_kernel, gemm_f16_kernel for the shapes it does not take; ff_fused_kernel = LayerNorm + FeedForward and lnqkv_kernel = LayerNorm + q|k|v at C = 320, conv3x3_narrow_kernel = the output head; MFMA implicit-GEMM family: Linear, Conv2d 3x3/1x1, Conv3d (3,1,1))",
+                     "launches_per_step": gk["launches"],
+                     "algorithmic_tflop_per_step": round(gk["flops"] / 1e12, 3),
+                     "kernel_ms_per_step": round(gk["ms"], 3)},
+        "attention": {"kernel": "attn_spatial64p_kernel (72x128, 36x64 tokens) + attn_spatial_kernel", "achieved": round(
+            ak["flops"] / (ak["ms"] * 1e-3) / 1e12, 2), "unit": "TFLOP/s",
+            "algorithmic_tflop_per_step": round(ak["flops"] / 1e12, 3),
+            "kernel_ms_per_step": round(ak["ms"], 3), "launches_per_step": ak["launches"]},
+        "hip_event_ms_per_step_rank0": round(ev_ms / args.steps, 3),
+        "timing_stats": {"regions": len(region_ms), "steps_per_region": args.steps,
+                         "ms_per_step_sorted": [round(v, 3) for v in region_ms],
+                         "ms_per_step_median": round(region_ms[len(region_ms) // 2], 3),
+                         "reported_region": "first (max over ranks)"},
+        "per_rank_ms_per_step": [round(float(t[0]) * 1e3 / args.steps, 3) for t in per_rank],
+        "rccl_ranks": rccl_ranks,
+        "dist_backend": args.backend if dist is not None else None,
+        "gather_ms": round(gather_ms, 3), "gathered_shape": list(gathered.shape),
+        "output_finite": finite,
+        "workspace_gib": round(net.engine.ws.nbytes() / 2 ** 30, 2),
+    })
+    parity_ok = True
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity(net, sampler, fd, T, dev, 5, cond,
+                                                                         full=args.cpu_baseline_full)
+        parity_ok = out["parity"]["ok"]
+    elif world > 1:
+        out["cpu_baseline_note"] = ("N > 1 lines carry no cpu_baseline / parity: both are measured by the N = 1 "
+                                    "line only (BENCH contract: rank 0 at N = 1)")
+    return parity_ok
 
 
 if __name__ == "__main__":

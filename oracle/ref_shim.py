@@ -14,7 +14,10 @@ REF = Path("/root/reference/gcd-model")
 
 
 def available() -> bool:
-    return (REF / "sgm" / "modules" / "diffusionmodules" / "video_model.py").exists()
+    try:
+        return (REF / "sgm" / "modules" / "diffusionmodules" / "video_model.py").exists()
+    except OSError:         # a tree this user may not read counts as absent
+        return False
 
 
 def install() -> None:

@@ -7,6 +7,7 @@ Operands are fp16 with fp32 accumulation in both directions (activations and inc
 rounded once per contraction), so per-operator gradients carry ~2^-11 relative noise per operand:
 tolerance 3e-3 rel-L2 per operator, 5e-3 on the gradients of whole blocks / the whole network, as
 measured values are printed."""
+import gc
 import math
 
 import pytest
@@ -678,6 +679,9 @@ def test_activation_checkpointing_matches(gpu):
     for ck in (False, True):
         for p in net.parameters():
             p.grad = None
+        # an earlier test's model (reference cycles: gigabytes at full width) freed by the cyclic collector in the middle
+        # of the forward below would make `held` negative: collect it before the baseline is read
+        gc.collect()
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         base = torch.cuda.memory_allocated()

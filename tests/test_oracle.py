@@ -122,22 +122,21 @@ def test_random_init_is_vacuous_without_reseeding():
 
 
 def test_embedders_against_reference_if_mounted():
-    from oracle import ref_shim
-    if not ref_shim.available():
-        pytest.skip("/root/reference not mounted")
-    VideoUNet, *_ = ref_shim.reference_classes()
-    # re-check the restatement directly against the live reference at a second shape / seed
+    """The restatement against the reference at a second shape / seed, with the image_only_indicator path of
+    AlphaBlender: the reference's own forward is recorded in tests/golden/ref_checks_tiny.pt
+    (oracle/make_golden_ref_checks.py, which also rebuilds the inputs)."""
+    from oracle.make_golden_ref_checks import embedders_inputs
+    g = torch.load(GOLD / "ref_checks_tiny.pt")["embedders"]
     cfg = O.TINY
-    net = VideoUNet(**cfg.as_reference_kwargs()).eval()
-    shapes = {k: tuple(v.shape) for k, v in net.state_dict().items()}
-    sd = weights.synth_state_dict(shapes, salt=1)
-    net.load_state_dict(sd)
-    x, ts, ctx, y, ioi = _unet_inputs(cfg, 2, 8, 16, 9)
-    ioi[1, 0] = 1.0     # image_only_indicator path of AlphaBlender
+    with torch.device("meta"):
+        from gcd_amd.video_model import VideoUNet
+        shapes = {k: tuple(v.shape) for k, v in VideoUNet(**cfg.as_reference_kwargs()).state_dict().items()}
+    sd = weights.synth_state_dict(shapes, salt=g["salt"])
+    x, ts, ctx, y, ioi = embedders_inputs()
+    assert float(ioi.abs().sum()) > 0
     with torch.no_grad():
-        ref = net(x, ts, context=ctx, y=y, num_video_frames=2, image_only_indicator=ioi)
-        mine = O.unet_forward(sd, cfg, x, ts, ctx, y, 2, ioi)
-    assert rel_l2(mine, ref) < 2e-5
+        mine = O.unet_forward(sd, cfg, x, ts, ctx, y, g["T"], ioi)
+    assert rel_l2(mine, g["out"]) < 2e-5
 
 
 def test_oracle_full_width_cfg0_step_vs_reference_golden():
@@ -166,41 +165,33 @@ def test_oracle_gradients_match_live_reference():
     """The fine-tune step's parity chain (tests/test_backward_gpu.py) compares the HIP gradients with
     torch.autograd over the ORACLE; this pins that reference: autograd through the oracle restatement
     equals autograd through the unmodified reference modules (denoiser + L2 loss, TINY width), for the
-    input and for every parameter.  Build container only."""
-    from oracle import ref_shim
-    if not ref_shim.available():
-        pytest.skip("/root/reference not mounted")
-    VideoUNet, OpenAIWrapper, Denoiser, _ = ref_shim.reference_classes()
+    input and for every parameter.  The reference's run is recorded in tests/golden/ref_checks_tiny.pt
+    (oracle/make_golden_ref_checks.py: every parameter gradient by its norm, strided samples and seeded
+    projections of the whole tensor)."""
+    from oracle.make_golden_ref_checks import gradients_inputs, rel_err, unpack
+    g = torch.load(GOLD / "ref_checks_tiny.pt")["gradients"]
     cfg = O.TINY
-    net = VideoUNet(**cfg.as_reference_kwargs()).train()
-    shapes = {k: tuple(v.shape) for k, v in net.state_dict().items()}
-    sd = weights.synth_state_dict(shapes, salt=7)
-    net.load_state_dict(sd)
-    T, h, w = 2, 8, 8
-    noise, c, _ = weights.synth_inputs(2, T, h, w, cfg.context_dim, cfg.adm_in_channels + cfg.aux_emb_dim, 13)
-    g = torch.Generator().manual_seed(14)
-    target = torch.randn(noise.shape, generator=g)
-    sigma = torch.tensor([2.5, 2.5, 0.3, 0.3])
-    ioi = torch.zeros(2, T)
-    den = Denoiser(ref_shim.DENOISER_CFG)
-    x_ref = noise.clone().requires_grad_(True)
-    out = den(OpenAIWrapper(net), x_ref, sigma, c, num_video_frames=T, image_only_indicator=ioi)
-    ((out - target) ** 2).mean().backward()
+    with torch.device("meta"):
+        from gcd_amd.video_model import VideoUNet
+        shapes = {k: tuple(v.shape) for k, v in VideoUNet(**cfg.as_reference_kwargs()).state_dict().items()}
+    records = unpack(g["param_grads"], shapes)
+    sd = weights.synth_state_dict(shapes, salt=g["salt"])
     sdo = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    noise, c, target, sigma, ioi = gradients_inputs()
     x_o = noise.clone().requires_grad_(True)
-    out_o = O.denoise(sdo, cfg, x_o, sigma, c, T, ioi)
+    out_o = O.denoise(sdo, cfg, x_o, sigma, c, g["T"], ioi)
     ((out_o - target) ** 2).mean().backward()
-    assert rel_l2(out_o, out) < 2e-5 and rel_l2(x_o.grad, x_ref.grad) < 2e-5
+    assert rel_l2(out_o, g["out"]) < 2e-5 and rel_l2(x_o.grad, g["x_grad"]) < 2e-5
     checked = dead = 0
-    for name, p in net.named_parameters():
-        gr, go = p.grad, sdo[name].grad
+    for name, rec in records.items():
+        go = sdo[name].grad
         # q / k / norm2 of the one-key cross-attention: exactly 0 in exact arithmetic; the reference's SDPA
         # backward leaves ~1e-10 of rounding noise there
-        if gr is None or float(gr.abs().max()) < 1e-8:
+        if rec is None or rec["amax"] < 1e-8:
             assert go is None or float(go.abs().max()) < 1e-8, name
             dead += 1
             continue
         # (scalar blend logits are long cancelling sums: fp32 summation order shows at 1e-4)
-        assert rel_l2(go, gr) < (5e-5 if gr.numel() > 1 else 1e-3), name
+        assert go is not None and rel_err(go, rec) < (5e-5 if go.numel() > 1 else 1e-3), name
         checked += 1
     assert checked > 1000 and dead >= 64

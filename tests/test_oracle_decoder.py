@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import rel_l2
-from oracle import vae_decoder_ref as D, weights
+from oracle import ref_shim, vae_decoder_ref as D, weights
 
 GOLD = Path(__file__).resolve().parent / "golden"
 
@@ -94,7 +94,7 @@ def test_product_decoder_has_no_cpu_path_and_rejects_other_modes():
         VideoDecoder(**dict(kw, video_kernel_size=3))
 
 
-@pytest.mark.skipif(not Path("/root/reference/gcd-model").exists(), reason="reference tree not mounted")
+@pytest.mark.skipif(not ref_shim.available(), reason="reference tree not readable here")
 def test_golden_is_reproducible_from_the_reference(gold):
     """Build container only: the committed fixture is what the reference class computes today."""
     from oracle.make_golden_decoder import reference_decoder_class

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import rel_l2
-from oracle import vae_encoder_ref as E, weights
+from oracle import ref_shim, vae_encoder_ref as E, weights
 
 GOLD = Path(__file__).resolve().parent / "golden"
 
@@ -81,7 +81,7 @@ def test_product_encoder_has_the_reference_parameters(gold):
         Encoder(**dict(kw, resamp_with_conv=False))
 
 
-@pytest.mark.skipif(not Path("/root/reference/gcd-model").exists(), reason="reference tree not mounted")
+@pytest.mark.skipif(not ref_shim.available(), reason="reference tree not readable here")
 def test_golden_is_reproducible_from_the_reference(gold):
     from oracle.make_golden_encoder import reference_encoder_class
     enc = reference_encoder_class()(**E.TINY.as_reference_kwargs()).eval()

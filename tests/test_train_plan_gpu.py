@@ -486,19 +486,35 @@ def test_planned_engine_inputs_that_need_gradients_and_no_grad_forwards(gpu):
     from gcd_amd.train_plan import plan_for, unet_forward_planned
     net = _tiny(gpu, salt=5)
     s = _tiny_step_inputs(gpu, 43)
-    grads = {}
-    for name, fn in (("planned-entry", unet_forward_planned), ("autograd", TR.unet_forward_train)):
+    grads, calls = {}, []
+    engine = TR.unet_forward_train
+
+    def spy(*a, **kw):
+        calls.append((a, kw))
+        return engine(*a, **kw)
+    for name, fn in (("planned-entry", unet_forward_planned), ("autograd", engine)):
         y = s["y"].clone().requires_grad_()
         for p in net.parameters():
             p.grad = None
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)
-            out = fn(net, s["x"], s["ts"], s["ctx"], y, s["T"], s["ioi"], use_checkpoint=True)
+            TR.unet_forward_train = spy
+            try:
+                out = fn(net, s["x"], s["ts"], s["ctx"], y, s["T"], s["ioi"], use_checkpoint=True)
+            finally:
+                TR.unet_forward_train = engine
+        if name == "planned-entry":
+            # the planned entry handed the whole call, unchanged, to the operator-level engine
+            assert len(calls) == 1 and calls[0][1] == {"use_checkpoint": True}
+            assert all(u is v for u, v in zip(calls[0][0], (net, s["x"], s["ts"], s["ctx"], y, s["T"], s["ioi"])))
         ((out - s["tgt"]) ** 2).mean().mul(64.0).backward()
         torch.cuda.synchronize()
         assert y.grad is not None and float(y.grad.abs().max()) > 0
         grads[name] = y.grad.clone()
-    assert torch.equal(grads["planned-entry"], grads["autograd"])
+    # Two runs of that one engine, so equal but for the run-to-run order of its fp32 atomic sums (bias / per-frame-vector
+    # gradients; the time embedding's gradient, which y's is made from, sums all 44 emb_layers): not bit-equal, see
+    # test_backward_gpu.py::test_activation_checkpointing_matches for the same bar.  A wrong gradient would be O(1).
+    assert rel_l2(grads["planned-entry"], grads["autograd"]) < 1e-3
     plan = plan_for(net, True)
     with torch.no_grad():
         o1 = unet_forward_planned(net, s["x"], s["ts"], s["ctx"], s["y"], s["T"], s["ioi"], use_checkpoint=True)

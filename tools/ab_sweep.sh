@@ -23,7 +23,7 @@ for r in $(seq 1 "$ROUNDS"); do
   for v in "${VARIANTS[@]}"; do
     name=${v%%:*}
     envs=${v#*:}
-    line=$(env $envs python bench.py --steps 10 --warmup 3 --repeats 2 --no-cpu-baseline 2>/dev/null | tail -1)
+    line=$(env $envs python bench.py --full --steps 10 --warmup 3 --repeats 2 --no-cpu-baseline 2>/dev/null | tail -1)
     ms=$(python - "$line" <<'E'
 import json, sys
 try:

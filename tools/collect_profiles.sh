@@ -7,8 +7,8 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
-(cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/trace -o p -- python $ROOT/bench.py --steps 5 --warmup 2 \
+python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+(cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/trace -o p -- python $ROOT/bench.py --full --steps 5 --warmup 2 \
     --repeats 1 --no-cpu-baseline > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err)
 python tools/rocpd_stats.py $(find $OUT/trace -name "*_results.db" | head -1) --steps 8 > $OUT/kernel_stats.txt
 bash tools/collect_pmc.sh $TAG
@@ -34,5 +34,5 @@ du -sh $ROOT/gpurun_out
 ls -la $OUT
 # round 4: the CPU path timed at the metric's own shape beside the GPU number (one oracle step at 14x72x128, minutes)
 if [ "${GCD_CPU_FULL:-0}" = "1" ]; then
-  python bench.py --steps 10 --warmup 2 --repeats 1 --cpu-baseline-full > $OUT/bench_cpu_full.json 2> $OUT/bench_cpu_full.err
+  python bench.py --full --steps 10 --warmup 2 --repeats 1 --cpu-baseline-full > $OUT/bench_cpu_full.json 2> $OUT/bench_cpu_full.err
 fi

@@ -23,7 +23,7 @@ if [ "$have" -lt 2 ]; then echo "needs >= 2 GPUs" | tee -a $OUT/summary.txt; exi
 rc=0
 for n in 1 2 4 $N; do
   [ "$n" -gt "$N" ] && continue
-  python bench.py --gpus $n --steps 20 --warmup 3 > $OUT/bench_n$n.json 2> $OUT/bench_n$n.err || { echo "bench --gpus $n FAILED" | tee -a $OUT/summary.txt; rc=1; }
+  python bench.py --full --gpus $n --steps 20 --warmup 3 > $OUT/bench_n$n.json 2> $OUT/bench_n$n.err || { echo "bench --gpus $n FAILED" | tee -a $OUT/summary.txt; rc=1; }
   python - $OUT/bench_n$n.json $n <<'PY' | tee -a $OUT/summary.txt
 import json, sys
 try:

@@ -3,11 +3,11 @@ passes of bench.py that tools/pmc_traffic.py sums per kernel family (FETCH_SIZE,
 TCC_HIT_sum TCC_MISS_sum) plus the per-launch table of the instrumented step (`bench.py --dump-profile`):
 
     for C in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
-      rocprofv3 --pmc $C --kernel-trace --output-format csv -d gpurun_out/pmc_${C%% *} -o p -- \
-          python bench.py --steps 1 --warmup 1 --no-cpu-baseline --dump-profile gpurun_out/launches.json
+      rocprofv3 --pmc $C --kernel-trace --output-format csv -d out/pmc_${C%% *} -o p -- \
+          python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --dump-profile out/launches.json
     done
-    python tools/pmc_gemm_shapes.py gpurun_out/launches.json gpurun_out/pmc_FETCH_SIZE/p_counter_collection.csv \
-        gpurun_out/pmc_WRITE_SIZE/p_counter_collection.csv [gpurun_out/pmc_TCC_HIT_sum/p_counter_collection.csv]
+    python tools/pmc_gemm_shapes.py out/launches.json out/pmc_FETCH_SIZE/p_counter_collection.csv \
+        out/pmc_WRITE_SIZE/p_counter_collection.csv [out/pmc_TCC_HIT_sum/p_counter_collection.csv]
 
 The GEMM-family dispatches of the LAST step of the run (the instrumented eager step) are matched, in launch order,
 to the `gemm` records of the launch table (a split-K call is two dispatches: the K-slice kernel + the reduce).
