@@ -93,6 +93,7 @@ SIGNATURES = {
     "gcd_attn_transpose_v": (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _vp]),
     "gcd_attn_spatial_f16": (_i, [_vp, _i64, _vp, _i, _vp, _i64, _i, _i, _i, _i, _vp]),
     "gcd_attn_temporal_f16": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "gcd_attn_temporal_long_f16": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
     "gcd_softmax_rows_f16": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _vp]),
     "gcd_transpose_f16": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp]),
     "gcd_time_mix_unpack": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -118,6 +119,7 @@ SIGNATURES = {
     "gcd_attn_spatial_bwd_ws_bytes": (_i64, [_i, _i, _i]),
     "gcd_attn_spatial_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _f, _vp]),
     "gcd_attn_temporal_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "gcd_attn_temporal_long_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
     "gcd_cast_scale_f32_f16": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _f, _vp]),
     "gcd_cast_f32_bf16": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _vp]),
     "gcd_cast_colsum_f32": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _i64, _vp, _i, _vp, _vp]),

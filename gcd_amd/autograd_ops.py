@@ -1008,9 +1008,10 @@ class TemporalAttention(torch.autograd.Function):
         clips, T, HW, heads = ctx.dims
         dO = dO.contiguous()
         dqkv = torch.empty(qkv16.shape, dtype=_f32, device=dO.device)
-        check(_lib.load().gcd_attn_temporal_bwd(qkv16.data_ptr(), _ld(qkv16), dO.data_ptr(), _ld(dO),
-                                                dqkv.data_ptr(), _ld(dqkv), clips, T, HW, heads, _stream()),
-              "gcd_attn_temporal_bwd")
+        # T <= 16: gcd_attn_temporal_bwd; 17..64: gcd_attn_temporal_long_bwd (which refuses T > 64)
+        name = "gcd_attn_temporal_bwd" if T <= 16 else "gcd_attn_temporal_long_bwd"
+        check(getattr(_lib.load(), name)(qkv16.data_ptr(), _ld(qkv16), dO.data_ptr(), _ld(dO), dqkv.data_ptr(),
+                                         _ld(dqkv), clips, T, HW, heads, _stream()), name)
         return dqkv, None, None, None, None
 
 

@@ -439,10 +439,12 @@ def attn_spatial_bwd_ws_bytes(frames: int, S: int, heads: int) -> int:
 
 
 def attn_temporal(qkv16, out16, clips: int, T: int, HW: int, heads: int):
+    """Self-attention over the T frames of every (clip, pixel, head): T <= 16 on gcd_attn_temporal_f16,
+    17..64 on gcd_attn_temporal_long_f16 (which refuses T > 64)."""
     _need_gpu(qkv16, out16)
-    check(_lib.load().gcd_attn_temporal_f16(qkv16.data_ptr(), _ld(qkv16), out16.data_ptr(),
-                                            _ld(out16), clips, T, HW, heads, _stream()),
-          "gcd_attn_temporal_f16")
+    name = "gcd_attn_temporal_f16" if T <= 16 else "gcd_attn_temporal_long_f16"
+    check(getattr(_lib.load(), name)(qkv16.data_ptr(), _ld(qkv16), out16.data_ptr(), _ld(out16), clips, T, HW,
+                                     heads, _stream()), name)
     return out16
 
 

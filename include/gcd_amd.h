@@ -311,6 +311,10 @@ int gcd_attn_spatial_f16(const void* qkv, int64_t ld, const void* vt, int S_pad,
  * (video_attention.py:114,126-129 -> attention.py:331-335).  Rows are ((b*T + t)*HW + s).       */
 int gcd_attn_temporal_f16(const void* qkv, int64_t ld, void* out, int64_t ldo, int clips, int T,
                           int HW, int heads, void* stream);
+/* The same over 1 <= T <= 64 frames (the host takes it for T = 17..64).  ld: a multiple of 8, >= 3C;
+ * ldo: a multiple of 4, >= C; qkv 16-byte and out 8-byte aligned.                                  */
+int gcd_attn_temporal_long_f16(const void* qkv, int64_t ld, void* out, int64_t ldo, int clips, int T,
+                               int HW, int heads, void* stream);
 
 /* ---- first-stage decoder (VideoDecoder) helpers ------------------------------------------------ */
 /* y16[r, :] = softmax(x[r, :]) for an fp32 score matrix [R, C] (C % 4 == 0, C <= 16384): the softmax
@@ -429,6 +433,11 @@ int gcd_attn_spatial_bwd(const void* qkv16, int64_t ld, const void* out16, int64
 /* Backward of gcd_attn_temporal_f16 (T <= 16 tokens, d = 64): dqkv fp32 [M, 3C] from dO fp32 [M, C].  */
 int gcd_attn_temporal_bwd(const void* qkv16, int64_t ld, const float* dO, int64_t lddo, float* dqkv,
                           int64_t lddq, int clips, int T, int HW, int heads, void* stream);
+/* Backward of gcd_attn_temporal_long_f16 (1 <= T <= 64): dqkv fp32 [M, 3C] from dO fp32 [M, C], P recomputed from
+ * the fp16 q and k.  ld: a multiple of 8, >= 3C; lddo: a multiple of 4, >= C; lddq >= 3C; qkv16 and dO 16-byte
+ * aligned.                                                                                           */
+int gcd_attn_temporal_long_bwd(const void* qkv16, int64_t ld, const float* dO, int64_t lddo, float* dqkv,
+                               int64_t lddq, int clips, int T, int HW, int heads, void* stream);
 /* y16 = fp16(x * scale): gradients enter the fp16 GEMMs pre-scaled (loss scaling), the GEMM's s_acc
  * removes the factor in fp32.                                                                        */
 /* y = bfloat16(x) (round to nearest even), for operand_bf16 GEMMs; x fp32 or (the _f16 form) fp16.      */

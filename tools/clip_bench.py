@@ -1,8 +1,9 @@
 """tools/clip_bench.py — one whole clip on one MI355X: 25-step EulerEDM + CFG sampling loop on the HIP
-VideoUNet (14 x 72 x 128 latents) followed by the HIP first-stage decode to 14 frames of 576 x 1024,
+VideoUNet (14 x 72 x 128 latents; --frames N for N-frame clips, 1..60 under CFG at this size) followed by the HIP
+first-stage decode to the clip's frames at 576 x 1024,
 i.e. what DiffusionEngine.sample_video + decode_first_stage do per clip after the conditioner.
 
-    python tools/clip_bench.py [--steps 25] [--clips 2] [--json out.json]
+    python tools/clip_bench.py [--steps 25] [--clips 2] [--frames 14] [--json out.json]
 
 Random-init weights of the real architectures (no checkpoints offline), synthetic conditioning."""
 from __future__ import annotations
@@ -23,6 +24,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--clips", type=int, default=2)
+    ap.add_argument("--frames", type=int, default=14, help="frames per clip (T)")
     ap.add_argument("--json", type=str, default="")
     a = ap.parse_args()
     import bench
@@ -32,7 +34,7 @@ def main():
     from gcd_amd.temporal_ae import VideoDecoder
     from gcd_amd.wrappers import OpenAIWrapper
     dev = torch.device("cuda:0")
-    T, h, w = 14, 72, 128
+    T, h, w = a.frames, 72, 128
     net = bench.build_model(dev)
     torch.manual_seed(1)
     dec = VideoDecoder(attn_type="vanilla", double_z=True, z_channels=4, resolution=256, in_channels=3,
@@ -69,7 +71,7 @@ def main():
             times.append((t1 - t0, t2 - t1))
     loop = sorted(t[0] for t in times)[len(times) // 2]
     decd = sorted(t[1] for t in times)[len(times) // 2]
-    res = dict(workload=f"{a.steps}-step EulerEDM + CFG loop at 14x72x128 latents + decode to 14x3x576x1024",
+    res = dict(workload=f"{a.steps}-step EulerEDM + CFG loop at {T}x72x128 latents + decode to {T}x3x576x1024",
                loop_s=round(loop, 3), decode_s=round(decd, 3), clip_s=round(loop + decd, 3),
                clips_per_s=round(1.0 / (loop + decd), 4), frames_per_s=round(T / (loop + decd), 2),
                sampler_path=sampler.last_path)

@@ -5,7 +5,7 @@ backward through gcd_amd.autograd_ops, AdamHIP step.  Reports wall time per phas
 TFLOP/s (12.53 TFLOP forward at this shape; backward = 2x forward; the re-forward of the
 activation checkpointing is executed but not counted).  Not the repo's headline metric.
 
-    python tools/train_step_bench.py [--steps 3] [--latent 32x48]
+    python tools/train_step_bench.py [--steps 3] [--latent 32x48] [--frames 14]
     torchrun --nproc-per-node N tools/train_step_bench.py --ddp      cfg4's data parallelism: one rank per GPU, the
         gradient exchange by training.GradBucketer on RCCL; reports the all-reduce time left EXPOSED after backward
 """
@@ -32,6 +32,7 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--latent", default="32x48")
     ap.add_argument("--clips", type=int, default=2)
+    ap.add_argument("--frames", type=int, default=14, help="frames per clip (T)")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"],
                     help="operand type of the GEMM-family contractions, forward and backward (cfg4 names bf16)")
     ap.add_argument("--checkpoint", default="net", choices=["net", "on", "off"],
@@ -51,7 +52,7 @@ def main():
         torch.cuda.set_device(local)
         dist.init_process_group(os.environ.get("GCD_DIST_BACKEND", "nccl"))
     dev = torch.device(f"cuda:{local}")
-    T = 14
+    T = a.frames
     h, w = (int(v) for v in a.latent.split("x"))
     BT = a.clips * T
     net = build_model(dev, seed=0).train()
@@ -100,7 +101,7 @@ def main():
             times.append((t1 - t0, t2 - t1, t3 - t2))
         finite = bool(torch.isfinite(loss))
     f, b, o = (sorted(t[i] for t in times)[len(times) // 2] for i in range(3))
-    tf_fwd = 12.531 * (h * w) / (32 * 48) * a.clips / 2
+    tf_fwd = 12.531 * (h * w) / (32 * 48) * a.clips / 2 * T / 14      # (temporal attention's T^2 share neglected)
     extra = {}
     if dist is not None:
         ex = sorted(exposed[1:])[len(exposed[1:]) // 2] if len(exposed) > 1 else exposed[0]
