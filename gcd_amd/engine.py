@@ -472,7 +472,10 @@ class UNetEngine:
         """x = ff(norm(x32 + addvec)) + (x32 + addvec) [blended with r2] as ONE launch (ff_fused_kernel.h, the LayerNorm
         form): the LayerNorm kernel, its fp16 output and the 660 MB hidden tensor never touch memory.  False = not taken
         (another level, too few tokens, switched off): the caller runs LayerNorm + two GEMMs."""
-        if "wp" not in F or self.fuse_layernorm or not ops.ff_fused_ok(M, F["w1"].shape[1], F["w1"].shape[0] // 2):
+        # (a frame of H * W % 32 != 0 tokens with a per-frame vector / blend factor goes the LayerNorm + two-GEMM way)
+        if "wp" not in F or self.fuse_layernorm or not ops.ff_fused_ok(
+                M, F["w1"].shape[1], F["w1"].shape[0] // 2, rows_per_vec=None if addvec is None else rows_per_vec,
+                rows_per_alpha=None if frame_alpha is None else rows_per_alpha):
             return False
         ln = dict(gamma=affine[0], beta=affine[1], addvec=addvec, rows_per_vec=rows_per_vec)
         kw = dict(r2=r2, out_kind=out_kind, frame_alpha=frame_alpha, rows_per_alpha=rows_per_alpha, ln=ln)

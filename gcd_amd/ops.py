@@ -213,8 +213,13 @@ _FF_FUSED_ON = os.environ.get("GCD_FF_FUSED", "1") != "0"
 FF_FUSED_MIN_TOKENS = int(os.environ.get("GCD_FF_FUSED_MIN_TOKENS", str(4 * 256 * 128)))
 
 
-def ff_fused_ok(M: int, C_: int, hidden: int, enabled: Optional[bool] = None) -> bool:
+def ff_fused_ok(M: int, C_: int, hidden: int, enabled: Optional[bool] = None, rows_per_vec: Optional[int] = None,
+                rows_per_alpha: Optional[int] = None) -> bool:
+    """rows_per_vec / rows_per_alpha: the per-frame geometry of a call with `addvec` / `frame_alpha` (None: not used).
+    gcd_ff_fused_f16 takes one vector / blend factor per 32-row wave tile and refuses anything else."""
     on = _FF_FUSED_ON if enabled is None else enabled
+    if (rows_per_vec is not None and rows_per_vec % 32) or (rows_per_alpha is not None and rows_per_alpha % 32):
+        return False
     return bool(on and M >= FF_FUSED_MIN_TOKENS and _lib.load().gcd_ff_fused_supported(M, C_, hidden))
 
 
