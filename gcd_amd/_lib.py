@@ -140,7 +140,7 @@ SIGNATURES = {
 
 # libgcd_amd_train.so (include/gcd_amd_train.h): kernels of the fine-tune step only
 TRAIN_LIB_PATH = _PKG / "libgcd_amd_train.so"
-TRAIN_ABI_VERSION = 2
+TRAIN_ABI_VERSION = 3
 
 
 class PackEntry(C.Structure):
@@ -175,6 +175,21 @@ TRAIN_SIGNATURES = {
     "gcd_smallm_wgrad": (_i, [_vp, _i, _i, _vp]),
 }
 
+# the deterministic reductions (include/gcd_amd_train_det.h; gcd_amd/csrc/train_det.hip), same shared object
+TRAIN_DET_SIGNATURES = {
+    "gcd_rowblock_sum_det_scratch_floats": (_i64, [_i64, _i, _i64]),
+    "gcd_rowblock_sum_det_f32": (_i, [_vp, _i64, _i64, _i, _i64, _vp, _vp, _i64, _vp]),
+    "gcd_layernorm_bwd_det_scratch_floats": (_i64, [_i64, _i]),
+    "gcd_layernorm_bwd_det": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _vp, _f, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "gcd_cast_colsum_det_scratch_floats": (_i64, [_i64, _i, _i64]),
+    "gcd_cast_colsum_det_f32": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _i64, _vp, _i, _vp, _vp, _i64, _vp]),
+    "gcd_blend_bwd_det_scratch_floats": (_i64, [_i64, _i, _i64]),
+    "gcd_blend_bwd_det_f32": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i64, _vp, _i64, _i, _vp, _i64, _vp,
+                                   _vp, _i64, _vp]),
+    "gcd_smallm_dgrad_det_scratch_floats": (_i64, [_i]),
+    "gcd_smallm_dgrad_det": (_i, [_vp, _i, _i, _vp, _i64, _vp]),
+}
+
 _lib = None
 _train = None
 
@@ -187,7 +202,7 @@ def load_train() -> C.CDLL:
     if not TRAIN_LIB_PATH.exists():
         raise GcdError(f"{TRAIN_LIB_PATH} is missing: run `python -m gcd_amd.csrc.build` (needs hipcc)")
     lib = C.CDLL(str(TRAIN_LIB_PATH))
-    for name, (res, args) in TRAIN_SIGNATURES.items():
+    for name, (res, args) in list(TRAIN_SIGNATURES.items()) + list(TRAIN_DET_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

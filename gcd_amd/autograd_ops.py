@@ -67,6 +67,33 @@ def set_train_dtype(name: str) -> None:
     FWD_DTYPE = GRAD_DTYPE = _chk_dtype(name)
 
 
+# Deterministic reductions (include/gcd_amd_train_det.h): the five sums of the backward pass that otherwise use fp32
+# read-modify-write adds in whatever order the workgroups arrive (row-block sums, LayerNorm's affine gradients, cast +
+# column sums, the blender's d_alpha, the few-row dgrads) run as partial sums + an ordered fold, so that one step — and a
+# seeded run — is bit-reproducible.  Off by default: the default path is unchanged bit for bit.
+DETERMINISTIC = os.environ.get("GCD_TRAIN_DETERMINISTIC", "0") == "1"
+DET_CALLS = {}          # calls per deterministic entry (tests assert that the default mode makes none)
+
+
+def set_deterministic(on: bool) -> None:
+    """Process-level switch of the deterministic reductions (default: the environment variable GCD_TRAIN_DETERMINISTIC)."""
+    global DETERMINISTIC
+    if not isinstance(on, bool):
+        raise ValueError(f"deterministic must be True or False, got {on!r}")
+    DETERMINISTIC = on
+
+
+def _det_call(name: str, scratch_floats: int, device, call) -> None:
+    """One deterministic entry: `call(lib, scratch_ptr, scratch_floats)`; the partial sums live in the training workspace
+    (one per device and stream, consumed by the entry's own fold before anything else on that stream runs)."""
+    lib = _lib.load_train()
+    ws = _train_ws(device)
+    if scratch_floats > ws.numel():
+        raise _lib.GcdError(f"{name}: needs {scratch_floats} floats of scratch, the training workspace holds {ws.numel()}")
+    DET_CALLS[name] = DET_CALLS.get(name, 0) + 1
+    _lib.check_train(call(lib, ws.data_ptr(), ws.numel()), name)
+
+
 def _dt(name: str) -> torch.dtype:
     return _bf16 if name == "bf16" else _f16
 
@@ -273,6 +300,13 @@ def _cast16_colsum(dy32: torch.Tensor, dtype: torch.dtype, rows_per_block: Optio
     # atomics land there directly (no fill, no copy)
     sums = out_sums if out_sums is not None else _zeros(M // rows_per_block, N, dy32.device)
     # total (planned engine): the bias's slot, receiving the sum over all row blocks in the same pass
+    if DETERMINISTIC:
+        _det_call("gcd_cast_colsum_det_f32",
+                  int(_lib.load_train().gcd_cast_colsum_det_scratch_floats(M, N, rows_per_block)), dy32.device,
+                  lambda lib, sp, sn: lib.gcd_cast_colsum_det_f32(
+                      dy32.data_ptr(), _ld(dy32), y.data_ptr(), _ld(y), M, N, rows_per_block, sums.data_ptr(),
+                      int(dtype == _bf16), 0 if total is None else total.data_ptr(), sp, sn, _stream()))
+        return y, sums
     check(_lib.load().gcd_cast_colsum_f32(dy32.data_ptr(), _ld(dy32), y.data_ptr(), _ld(y), M, N, rows_per_block,
                                           sums.data_ptr(), int(dtype == _bf16), 0 if total is None else total.data_ptr(),
                                           _stream()), "gcd_cast_colsum_f32")
@@ -322,6 +356,11 @@ def _colsum(x32: torch.Tensor, rows_per_block: Optional[int] = None) -> torch.Te
     M, N = x32.shape
     rows = M if rows_per_block is None else rows_per_block
     out = _zeros(M // rows, N, x32.device)
+    if DETERMINISTIC:
+        _det_call("gcd_rowblock_sum_det_f32", int(_lib.load_train().gcd_rowblock_sum_det_scratch_floats(M, N, rows)),
+                  x32.device, lambda lib, sp, sn: lib.gcd_rowblock_sum_det_f32(
+                      x32.data_ptr(), _ld(x32), M, N, rows, out.data_ptr(), sp, sn, _stream()))
+        return out
     check(_lib.load().gcd_rowblock_sum_f32(x32.data_ptr(), _ld(x32), M, N, rows, out.data_ptr(), _stream()),
           "gcd_rowblock_sum_f32")
     return out
@@ -672,6 +711,13 @@ def _ln_bwd(x, dy, g32, eps, dest=None, dx_add=None):
     else:
         dgb = torch.zeros(2, Cc, dtype=_f32, device=x.device)      # one fill for both accumulators
         dg, db = dgb[0], dgb[1]
+    if DETERMINISTIC:
+        _det_call("gcd_layernorm_bwd_det", int(_lib.load_train().gcd_layernorm_bwd_det_scratch_floats(M, Cc)), x.device,
+                  lambda lib, sp, sn: lib.gcd_layernorm_bwd_det(
+                      x.data_ptr(), _ld(x), dy.data_ptr(), _ld(dy), M, Cc, g32.data_ptr(), eps, dx.data_ptr(), _ld(dx),
+                      dg.data_ptr(), db.data_ptr(), 0 if dx_add is None else dx_add.data_ptr(),
+                      0 if dx_add is None else _ld(dx_add), sp, sn, _stream()))
+        return dx, dg, db
     check(_lib.load().gcd_layernorm_bwd(x.data_ptr(), _ld(x), dy.data_ptr(), _ld(dy), M, Cc, g32.data_ptr(),
                                         eps, dx.data_ptr(), _ld(dx), dg.data_ptr(), db.data_ptr(),
                                         0 if dx_add is None else dx_add.data_ptr(), 0 if dx_add is None else _ld(dx_add),

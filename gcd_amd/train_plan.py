@@ -196,7 +196,10 @@ class _SmallGroup:
         def _ptr(t):
             return 0 if t is None else t.data_ptr()
         wg = mode == "wgrad"
-        sig = (mode, plan.accumulate if wg else False) + tuple(
+        # deterministic dgrad (gcd_smallm_dgrad_det): one workgroup per (problem, k chunk), `reserved` = the first problem
+        # of the table with the same dx — another table than the default mode's, so the mode is part of the signature
+        det = mode == "dgrad" and A.DETERMINISTIC
+        sig = (mode, plan.accumulate if wg else False, det) + tuple(
             (_ptr(it["x"]), _ptr(it["y"]), _ptr(it.get("dy")), _ptr(it["dx"]), _ptr(it["w"]), _ptr(it["b"]),
              tuple(it["x"].shape), it["x"].stride(0), it["y"].stride(0), it["w"].shape[0],
              0 if it.get("dy") is None else it["dy"].stride(0), 0 if it["dx"] is None else it["dx"].stride(0),
@@ -214,6 +217,7 @@ class _SmallGroup:
             raise RuntimeError(f"train_plan: the few-row problem table {self.name}/{mode} would be rebuilt inside a stream "
                                "capture (its pointers, shapes or flags differ from the warm-up steps)")
         probs, block0 = [], 0
+        heads: Dict[tuple, int] = {}
         for it in self.items:
             x, w, y = it["x"], it["w"], it["y"]
             Mtot, K = x.shape
@@ -238,6 +242,12 @@ class _SmallGroup:
                             continue
                         p.dx, p.lddx = it["dx"][m0:].data_ptr(), it["dx"].stride(0)
                         p.flags = (1 if it["dx_silu"] else 0) | 4
+                        if det:
+                            head = heads.setdefault((p.dx, M, K, p.lddx), len(probs))
+                            p.reserved = head
+                            block0 += (K + 255) // 256
+                            probs.append(p)
+                            continue
                     else:
                         if not w.requires_grad:
                             continue
@@ -273,7 +283,10 @@ class _SmallGroup:
         self._tabs.pop("wgrad", None)
         lib = _lib.load_train()
         dev, n, blocks = self._table("dgrad", plan)
-        if n:
+        if n and A.DETERMINISTIC:
+            A._det_call("gcd_smallm_dgrad_det", int(lib.gcd_smallm_dgrad_det_scratch_floats(blocks)), self.device,
+                        lambda lib_, sp, sn: lib_.gcd_smallm_dgrad_det(dev.data_ptr(), n, blocks, sp, sn, _stream()))
+        elif n:
             _lib.check_train(lib.gcd_smallm_dgrad(dev.data_ptr(), n, blocks, _stream()), "gcd_smallm_dgrad")
         dev, n, blocks = self._table("wgrad", plan)
         if n:
@@ -856,6 +869,14 @@ class TrainPlan:
         d_xs, d_xt = (torch.empty_like(dy) if want_xs else None), torch.empty_like(dy)
         want = blender.merge_strategy != "fixed" and blender.mix_factor.requires_grad
         dal = self._dalpha[slot] if want else None
+        if A.DETERMINISTIC:
+            M_, C_ = dy.shape
+            A._det_call("gcd_blend_bwd_det_f32", int(_lib.load_train().gcd_blend_bwd_det_scratch_floats(M_, C_, rows)),
+                        self.device, lambda lib, sp, sn: lib.gcd_blend_bwd_det_f32(
+                            dy.data_ptr(), dy.stride(0), xs.data_ptr(), xs.stride(0), xt.data_ptr(), xt.stride(0),
+                            a.data_ptr(), M_, C_, rows, 0 if d_xs is None else d_xs.data_ptr(), dy.stride(0), 0,
+                            d_xt.data_ptr(), d_xt.stride(0), 0 if dal is None else dal.data_ptr(), sp, sn, _stream()))
+            return d_xs, d_xt
         _lib.check_train(_lib.load_train().gcd_blend_bwd_f32(
             dy.data_ptr(), dy.stride(0), xs.data_ptr(), xs.stride(0), xt.data_ptr(), xt.stride(0), a.data_ptr(),
             dy.shape[0], dy.shape[1], rows, 0 if d_xs is None else d_xs.data_ptr(), dy.stride(0), 0, d_xt.data_ptr(),
@@ -1120,7 +1141,7 @@ class GraphedPlan:
     def forward(self, x, timesteps, context, y, T, ioi):
         plan = self.plan
         sig = (tuple(x.shape), tuple(timesteps.shape), tuple(context.shape), tuple(y.shape), tuple(ioi.shape), T,
-               A.FWD_DTYPE, A.GRAD_DTYPE, plan.checkpoint_policy, x.dtype, context.dtype, y.dtype)
+               A.FWD_DTYPE, A.GRAD_DTYPE, plan.checkpoint_policy, x.dtype, context.dtype, y.dtype, A.DETERMINISTIC)
         if sig != self.sig:
             self._reset(sig)
         if self.g_fwd is None and self.calls < self.WARMUP:

@@ -153,6 +153,13 @@ def set_train_engine(name: str) -> None:
 
 
 set_train_engine(os.environ.get("GCD_TRAIN_ENGINE", "planned"))
+# Bit-reproducible steps: the backward pass's five order-dependent fp32 sums run as partial sums + an ordered fold
+# (autograd_ops.set_deterministic; GCD_TRAIN_DETERMINISTIC=1).  Off by default.
+set_deterministic = A.set_deterministic
+
+
+def is_deterministic() -> bool:
+    return A.DETERMINISTIC
 _ADAM_MULTI = os.environ.get("GCD_ADAM_MULTI", "1") != "0"
 
 
@@ -263,16 +270,24 @@ class TrainDenoiser(nn.Module):
     """Denoiser.forward (denoiser.py:23-49) over OpenAIWrapper.forward (wrappers.py:23-34) with the
     training-mode UNet underneath: `denoiser(network, input, sigma, cond, **kwargs)`."""
 
-    def __init__(self, scaling_config: Dict, use_checkpoint: Optional[bool] = None, engine: Optional[str] = None):
+    def __init__(self, scaling_config: Dict, use_checkpoint: Optional[bool] = None, engine: Optional[str] = None,
+                 deterministic: Optional[bool] = None):
         super().__init__()
         self.scaling = instantiate_from_config(scaling_config)
         self.use_checkpoint = use_checkpoint        # None: follow the network's `use_checkpoint`
         if engine not in (None, "planned", "autograd"):
             raise ValueError(f"train engine must be 'planned' or 'autograd', got {engine!r}")
         self.engine = engine                        # None: the process default (set_train_engine / GCD_TRAIN_ENGINE)
+        if deterministic is not None and not isinstance(deterministic, bool):
+            raise ValueError(f"deterministic must be None, True or False, got {deterministic!r}")
+        # None: the process default (set_deterministic / GCD_TRAIN_DETERMINISTIC).  True / False: this denoiser sets the
+        # process-level switch at each of its forward passes — the backward pass that follows runs in the same mode
+        self.deterministic = deterministic
 
     def forward(self, network, input, sigma, cond, **additional_model_inputs):
         unet = getattr(network, "diffusion_model", network)
+        if self.deterministic is not None:
+            A.set_deterministic(self.deterministic)
         sigma_shape = sigma.shape
         s = append_dims(sigma, input.ndim)
         c_skip, c_out, c_in, c_noise = self.scaling(s)

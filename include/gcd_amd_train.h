@@ -10,7 +10,7 @@
 extern "C" {
 #endif
 
-#define GCD_AMD_TRAIN_ABI_VERSION 2
+#define GCD_AMD_TRAIN_ABI_VERSION 3
 
 int gcd_train_abi_version(void);
 const char* gcd_train_last_error(void);
