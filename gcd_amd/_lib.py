@@ -190,6 +190,42 @@ TRAIN_DET_SIGNATURES = {
     "gcd_smallm_dgrad_det": (_i, [_vp, _i, _i, _vp, _i64, _vp]),
 }
 
+
+
+# the device-resident optimizer step (include/gcd_amd_train_optim.h; gcd_amd/csrc/train_optim.hip), same shared object
+OPTIM_CHUNK = 16384
+
+
+class OptimState(C.Structure):
+    """gcd_optim_state: 64 bytes of device memory (fp32 / int32 only)."""
+    _fields_ = [("step", C.c_int32), ("lr", _f), ("loss_scale", _f), ("growth_tracker", C.c_int32),
+                ("found_inf", C.c_int32), ("grad_norm", _f), ("clip_coef", _f), ("skipped_total", C.c_int32),
+                ("ema_num_updates", C.c_int32), ("gfactor", _f), ("bc1", _f), ("bc2_sqrt", _f), ("ema_omd", _f),
+                ("reserved", C.c_int32 * 3)]
+
+
+class OptimTensor(C.Structure):
+    """gcd_optim_tensor: one entry of the device table."""
+    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("ema", _vp), ("n", _i64),
+                ("chunk0", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimConfig(C.Structure):
+    """gcd_optim_config: hyper-parameters, host memory."""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("grad_scale", _f), ("max_norm", _f), ("growth_factor", _f), ("backoff_factor", _f), ("ema_decay", _f),
+                ("growth_interval", C.c_int32), ("dynamic_scale", C.c_int32), ("decoupled", C.c_int32),
+                ("use_ema", C.c_int32), ("reserved", C.c_int32), ("ema_count", _vp)]
+
+
+TRAIN_OPTIM_SIGNATURES = {
+    "gcd_optim_gradstat_scratch_floats": (_i64, [_i64]),
+    "gcd_optim_gradstat": (_i, [_vp, _i, _i64, C.POINTER(OptimConfig), _vp, _vp, _i64, _vp]),
+    "gcd_optim_advance": (_i, [C.POINTER(OptimConfig), _vp, _vp]),
+    "gcd_optim_apply": (_i, [_vp, _i, _i64, C.POINTER(OptimConfig), _vp, _vp]),
+    "gcd_ema_update": (_i, [_vp, _i, _i64, C.POINTER(OptimConfig), _vp, _vp]),
+}
+
 _lib = None
 _train = None
 
@@ -202,7 +238,8 @@ def load_train() -> C.CDLL:
     if not TRAIN_LIB_PATH.exists():
         raise GcdError(f"{TRAIN_LIB_PATH} is missing: run `python -m gcd_amd.csrc.build` (needs hipcc)")
     lib = C.CDLL(str(TRAIN_LIB_PATH))
-    for name, (res, args) in list(TRAIN_SIGNATURES.items()) + list(TRAIN_DET_SIGNATURES.items()):
+    for name, (res, args) in (list(TRAIN_SIGNATURES.items()) + list(TRAIN_DET_SIGNATURES.items())
+                              + list(TRAIN_OPTIM_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -30,8 +30,9 @@ HEADERS = [CSRC / "common.h", CSRC / "gemm_common.h", CSRC / "ff_fused_kernel.h"
 # `sources_digest()`: they cannot change a kernel the sampler step launches.
 LIB_TRAIN = PKG / "libgcd_amd_train.so"
 STAMP_TRAIN = PKG / ".libgcd_amd_train.stamp"
-TRAIN_SOURCES = ["train_wgrad.hip", "train_ops.hip", "train_det.hip"]
-TRAIN_HEADERS = [ROOT / "include" / "gcd_amd_train.h", ROOT / "include" / "gcd_amd_train_det.h", CSRC / "train_wgrad_kernel.h"]
+TRAIN_SOURCES = ["train_wgrad.hip", "train_ops.hip", "train_det.hip", "train_optim.hip"]
+TRAIN_HEADERS = [ROOT / "include" / "gcd_amd_train.h", ROOT / "include" / "gcd_amd_train_det.h",
+                 ROOT / "include" / "gcd_amd_train_optim.h", CSRC / "train_wgrad_kernel.h"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast"]

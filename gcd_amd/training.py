@@ -436,10 +436,28 @@ class StandardDiffusionLoss(nn.Module):
 # ------------------------------------------------------------------------------------------------
 class AdamHIP:
     """torch.optim.Adam (lr, betas, eps, weight_decay; no amsgrad) driven by gcd_adam_step.
-    `grad_scale` undoes a static loss scale (and / or a 1 / world_size)."""
+    `grad_scale` undoes a static loss scale (and / or a 1 / world_size).
+
+    With any of `decoupled_weight_decay`, `max_grad_norm`, `loss_scale`, `ema` (or `device_state=True`) the step is the
+    device-resident one of include/gcd_amd_train_optim.h instead: one reduction pass over the gradients (only when clipping
+    or dynamic loss scaling asks for it), one fused update pass, a 64-byte state block in device memory between them — the
+    step count, the learning rate, the loss scale, "a gradient was not finite" and the clip coefficient never visit the host,
+    so `step()` neither synchronises nor allocates and can be captured in a graph.
+      decoupled_weight_decay  torch.optim.AdamW's decay (p *= 1 - lr * weight_decay) instead of Adam's (g += weight_decay * p)
+      max_grad_norm           torch.nn.utils.clip_grad_norm_ on the unscaled gradients
+      loss_scale              a fixed float, or "dynamic": torch.amp.GradScaler's rule (init_scale, growth_factor,
+                              backoff_factor, growth_interval); multiply the loss with `opt.scale(loss)`.  A step whose
+                              gradients are not finite leaves p, m, v and the step count untouched
+      ema                     a `gcd_amd.ema.LitEma`: its shadows are updated in the same pass, from the fresh weights (also on
+                              a skipped step, as the reference's on_train_batch_end does).  Do not call `ema(model)` as well
+    In this mode gradients must be contiguous fp32 tensors (what both training engines write); a parameter whose `.grad`
+    is None gets the EMA part only.  `stats()` is the one call that synchronises."""
 
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 2e-5, betas=(0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 0.0):
+                 eps: float = 1e-8, weight_decay: float = 0.0, *, decoupled_weight_decay: bool = False,
+                 max_grad_norm: Optional[float] = None, loss_scale=None, ema=None, device_state: Optional[bool] = None,
+                 init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000):
         self.params = [p for p in params if p.requires_grad]
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.state = [(torch.zeros_like(p, dtype=torch.float32), torch.zeros_like(p, dtype=torch.float32))
@@ -447,6 +465,207 @@ class AdamHIP:
         self.step_count = 0
         self._touched = {}       # id(p) -> the moments of p have been written at least once
         self._tables = None      # cached ctypes pointer tables of (params, m, v)
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self.max_grad_norm = max_grad_norm
+        self.loss_scale = loss_scale
+        self.ema = ema
+        options = decoupled_weight_decay or max_grad_norm is not None or loss_scale is not None or ema is not None
+        self.device_state = bool(options) if device_state is None else bool(device_state)
+        if options and not self.device_state:
+            raise ValueError("AdamHIP: decoupled_weight_decay, max_grad_norm, loss_scale and ema need the device-resident "
+                             "step (device_state=False was given)")
+        if self.device_state:
+            self._init_device_state(init_scale, growth_factor, backoff_factor, growth_interval)
+
+    # -- the device-resident step (include/gcd_amd_train_optim.h) -----------------------------------------------------------
+    def _init_device_state(self, init_scale, growth_factor, backoff_factor, growth_interval) -> None:
+        from . import _lib
+        from .ema import DeviceTable, LitEma, new_state_block
+        if self.max_grad_norm is not None and not (isinstance(self.max_grad_norm, (int, float)) and self.max_grad_norm > 0):
+            raise ValueError(f"max_grad_norm must be None or a positive number, got {self.max_grad_norm!r}")
+        ls = self.loss_scale
+        self.dynamic_scale = isinstance(ls, str)
+        if self.dynamic_scale:
+            if ls != "dynamic":
+                raise ValueError(f"loss_scale must be None, a positive float or 'dynamic', got {ls!r}")
+            if not (growth_factor > 1.0 and 0.0 < backoff_factor < 1.0 and int(growth_interval) >= 1 and init_scale > 0.0):
+                raise ValueError("dynamic loss scaling needs init_scale > 0, growth_factor > 1, 0 < backoff_factor < 1, "
+                                 "growth_interval >= 1")
+            scale0 = float(init_scale)
+        elif ls is None:
+            scale0 = 1.0
+        elif isinstance(ls, (int, float)) and not isinstance(ls, bool) and ls > 0 and math.isfinite(ls):
+            scale0 = float(ls)
+        else:
+            raise ValueError(f"loss_scale must be None, a positive float or 'dynamic', got {ls!r}")
+        if self.ema is not None and not isinstance(self.ema, LitEma):
+            raise ValueError(f"ema must be a gcd_amd.ema.LitEma, got {type(self.ema).__name__}")
+        if not self.params:
+            raise ValueError("AdamHIP: no trainable parameter")
+        self._scaler = dict(growth_factor=float(growth_factor), backoff_factor=float(backoff_factor),
+                            growth_interval=int(growth_interval))
+        self._device = self.params[0].device
+        self._state_block = new_state_block(self._device, lr=float(self.lr), loss_scale=scale0)
+        self._state_f32 = self._state_block.view(torch.float32)
+        self._table = DeviceTable("AdamHIP")
+        self._scratch = None
+        self._cfg = _lib.OptimConfig()
+        self.launches_per_step = 0
+
+    def _fill_config(self, grad_scale: float) -> None:
+        c = self._cfg
+        c.beta1, c.beta2, c.eps, c.weight_decay = self.betas[0], self.betas[1], self.eps, self.weight_decay
+        c.grad_scale = grad_scale
+        c.max_norm = 0.0 if self.max_grad_norm is None else float(self.max_grad_norm)
+        c.growth_factor, c.backoff_factor = self._scaler["growth_factor"], self._scaler["backoff_factor"]
+        c.growth_interval = self._scaler["growth_interval"]
+        c.dynamic_scale = int(self.dynamic_scale)
+        c.decoupled = int(self.decoupled_weight_decay)
+        if self.ema is not None:
+            self.ema.fill_config(c, self._device)
+        else:
+            c.use_ema, c.ema_count = 0, None
+
+    def _step_device(self, grad_scale: float) -> None:
+        import ctypes as C
+        from . import _lib
+        dev = self._device
+        if dev.type != "cuda":
+            raise _lib.GcdError("AdamHIP.step runs on the GPU; gcd_amd has no CPU fallback")
+        ema = self.ema
+        rows = []
+        for p, (m, v) in zip(self.params, self.state):
+            g = p.grad
+            if g is not None and (g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev):
+                raise _lib.GcdError(f"AdamHIP: the device-resident step needs contiguous fp32 gradients on {dev}, got "
+                                    f"{g.dtype}, strides {g.stride()}, on {g.device}")
+            assert p.is_contiguous() and p.dtype == torch.float32
+            s = None if ema is None else ema.shadow_of(p)
+            rows.append((p.data_ptr(), 0 if g is None else g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                         0 if s is None else s.data_ptr(), p.numel()))
+        tab = self._table
+        tab.update(rows, dev)
+        reduce = self.max_grad_norm is not None or self.dynamic_scale
+        if reduce and (self._scratch is None or self._scratch.numel() < tab.chunks):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("AdamHIP: the reduction scratch would be allocated inside a stream capture")
+            self._scratch = torch.empty((tab.chunks + 3) // 4 * 4, dtype=torch.float32, device=dev)
+        self._fill_config(float(grad_scale))
+        lib, stream = _lib.load_train(), torch.cuda.current_stream().cuda_stream
+        cfg, st = C.byref(self._cfg), self._state_block.data_ptr()
+        if reduce:
+            _lib.check_train(lib.gcd_optim_gradstat(tab.dev.data_ptr(), tab.count, tab.chunks, cfg, st,
+                                                    self._scratch.data_ptr(), self._scratch.numel(), stream),
+                             "gcd_optim_gradstat")
+        else:
+            _lib.check_train(lib.gcd_optim_advance(cfg, st, stream), "gcd_optim_advance")
+        _lib.check_train(lib.gcd_optim_apply(tab.dev.data_ptr(), tab.count, tab.chunks, cfg, st, stream), "gcd_optim_apply")
+        self.launches_per_step = 3 if reduce else 2
+        # the parameters were written through raw pointers (see step())
+        A.PACK.clear()
+
+    def scale(self, loss: torch.Tensor) -> torch.Tensor:
+        """loss x the loss scale of this step, read from the state block on the device (no synchronisation)."""
+        if not self.device_state:
+            raise ValueError("AdamHIP.scale needs the device-resident step (loss_scale=...)")
+        return loss * self._state_f32[2]
+
+    def set_lr(self, lr: float) -> None:
+        """The learning rate of the following steps; in the device-resident mode a stream-ordered write into the state
+        block (the hook a LambdaLR-style schedule needs)."""
+        self.lr = float(lr)
+        if self.device_state:
+            self._state_f32[1].fill_(self.lr)
+
+    def stats(self) -> Dict[str, float]:
+        """The state block as a dict — the one call that synchronises."""
+        if not self.device_state:
+            return {"step": self.step_count, "lr": self.lr}
+        from .ema import read_state_block
+        st = read_state_block(self._state_block)
+        self.step_count = int(st.step)
+        return {"step": int(st.step), "lr": float(st.lr), "loss_scale": float(st.loss_scale),
+                "growth_tracker": int(st.growth_tracker), "found_inf": bool(st.found_inf),
+                "grad_norm": float(st.grad_norm), "clip_coef": float(st.clip_coef),
+                "skipped_steps": int(st.skipped_total), "ema_num_updates": int(st.ema_num_updates)}
+
+    # -- checkpoints: torch.optim.Adam's own format ------------------------------------------------------------------------
+    SCALER_KEY = "gcd_amd_scaler"
+
+    def state_dict(self) -> dict:
+        """torch.optim.Adam.state_dict()'s layout (loads into torch.optim.Adam / AdamW over the same parameters): per
+        parameter index {step, exp_avg, exp_avg_sq} — the tensors themselves, as torch returns them — and one param
+        group.  The loss-scaler state rides under one extra top-level key in torch.amp.GradScaler.state_dict()'s keys."""
+        st = self.stats()
+        step = int(st["step"])
+        state = {}
+        for i, (p, (m, v)) in enumerate(zip(self.params, self.state)):
+            if self.device_state or self._touched.get(id(p), False):
+                state[i] = {"step": torch.tensor(float(step)), "exp_avg": m, "exp_avg_sq": v}
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
+                 "fused": None, "params": list(range(len(self.params)))}
+        out = {"state": state, "param_groups": [group]}
+        if self.device_state:
+            out[self.SCALER_KEY] = {"scale": st["loss_scale"], "growth_factor": self._scaler["growth_factor"],
+                                    "backoff_factor": self._scaler["backoff_factor"],
+                                    "growth_interval": self._scaler["growth_interval"],
+                                    "_growth_tracker": st["growth_tracker"], "skipped_steps": st["skipped_steps"]}
+        return out
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        """Load what `state_dict()` or `torch.optim.Adam(W).state_dict()` over the same parameters saved.  The moments are
+        copied into this optimizer's own tensors; every pointer table is rebuilt at the next step."""
+        from . import _lib
+        groups = sd.get("param_groups")
+        if not isinstance(groups, (list, tuple)) or len(groups) != 1:
+            raise _lib.GcdError("AdamHIP.load_state_dict: exactly one param group is supported")
+        group = groups[0]
+        if len(group["params"]) != len(self.params):
+            raise _lib.GcdError(f"AdamHIP.load_state_dict: the state has {len(group['params'])} parameters, this optimizer "
+                                f"{len(self.params)}")
+        if group.get("amsgrad", False) or group.get("maximize", False):
+            raise _lib.GcdError("AdamHIP.load_state_dict: amsgrad / maximize are not implemented")
+        state = sd.get("state", {})
+        ids = list(group["params"])
+        steps = {int(float(state[k]["step"])) for k in ids if k in state}
+        if len(steps) > 1:
+            raise _lib.GcdError(f"AdamHIP.load_state_dict: per-parameter step counts differ ({sorted(steps)}); this "
+                                "optimizer keeps one step count")
+        step = steps.pop() if steps else 0
+        for k, p, (m, v) in zip(ids, self.params, self.state):
+            ent = state.get(k)
+            if ent is None:
+                m.zero_()
+                v.zero_()
+                self._touched.pop(id(p), None)
+                continue
+            if tuple(ent["exp_avg"].shape) != tuple(m.shape) or tuple(ent["exp_avg_sq"].shape) != tuple(v.shape):
+                raise _lib.GcdError(f"AdamHIP.load_state_dict: parameter {k}: moments of shape "
+                                    f"{tuple(ent['exp_avg'].shape)}, parameter of shape {tuple(m.shape)}")
+            m.copy_(ent["exp_avg"])
+            v.copy_(ent["exp_avg_sq"])
+            self._touched[id(p)] = True
+        self.lr, self.betas = float(group["lr"]), tuple(group["betas"])
+        self.eps, self.weight_decay = float(group["eps"]), float(group["weight_decay"])
+        self.step_count = step
+        self._tables = None
+        if self.device_state:
+            from .ema import new_state_block, read_state_block
+            old = read_state_block(self._state_block)
+            sc = sd.get(self.SCALER_KEY)
+            fields = dict(step=step, lr=self.lr, loss_scale=float(old.loss_scale), growth_tracker=0, skipped_total=0,
+                          found_inf=int(old.found_inf), grad_norm=float(old.grad_norm), clip_coef=float(old.clip_coef))
+            if sc is not None:
+                fields.update(loss_scale=float(sc["scale"]), growth_tracker=int(sc["_growth_tracker"]),
+                              skipped_total=int(sc.get("skipped_steps", 0)))
+                if self.dynamic_scale:
+                    self._scaler = dict(growth_factor=float(sc["growth_factor"]), backoff_factor=float(sc["backoff_factor"]),
+                                        growth_interval=int(sc["growth_interval"]))
+            # in place: a captured step keeps pointing at this block
+            self._state_block.copy_(new_state_block(self._device, **fields))
+            self._table.reset()
 
     def zero_grad(self):
         for p in self.params:
@@ -454,6 +673,8 @@ class AdamHIP:
 
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0):
+        if self.device_state:
+            return self._step_device(grad_scale)
         import ctypes as C
         from . import _lib
         self.step_count += 1
