@@ -322,10 +322,22 @@ static int dispatch_tile(const GemmK& k, hipStream_t s) {
 // at most one residual, no fused LayerNorm, per-frame vectors / blend factors constant over a tile.
 static bool colstats_shape_ok(const gcd_gemm_desc* d) {
   if (d->out_kind != GCD_OUT_F32 || d->R2 || d->ln_out16) return false;
+  // the phase form of the x2 up-convolution: a wave's 64 low-res tokens must lie in one frame (gemm_p8.hip, P8_CONV_UP2)
+  if (d->mode == GCD_GEMM_CONV3X3 && d->upsample == 2)
+    return d->N % 320 == 0 && d->Hi > 0 && d->Wi > 0 && ((int64_t)d->Hi * d->Wi) % 64 == 0 && !d->R1 && !d->rowvec &&
+           !d->frame_alpha;
   if (d->M % 256 != 0 || d->N % 320 != 0) return false;
   if (d->rowvec && d->rows_per_vec % 256 != 0) return false;
   if (d->frame_alpha && d->rows_per_alpha % 256 != 0) return false;
   return true;
+}
+
+// 256 x 320 tiles of a launch on the tile kernels.  The phase form of the x2 up-convolution (upsample == 2) runs four
+// phase tiles per 256 LOW-RES tokens.
+static int64_t pp_tiles(const gcd_gemm_desc* d) {
+  const int64_t tn = (d->N + 319) / 320;
+  if (d->mode == GCD_GEMM_CONV3X3 && d->upsample == 2) return 4 * (((int64_t)d->M / 4 + 255) / 256) * tn;
+  return (int64_t)((d->M + 255) / 256) * tn;
 }
 
 // Implicit-GEMM geometry of a descriptor (conv3x3: pad 1 / stride 1-2 / fused x2 upsample /
@@ -336,6 +348,20 @@ static int validate_geometry(const gcd_gemm_desc* d) {
       return 0;
     case GCD_GEMM_CONV3X3:
       GCD_CHECK_ARG(d->zero_page, "gcd_gemm_f16: conv mode needs a zero page");
+      if (d->upsample == 2) {   // four 2 x 2 phase convolutions: W [4][N][4 Cin] (packing.pack_conv3x3_up_phases)
+        GCD_CHECK_ARG(d->Cin > 0 && d->Cin % 64 == 0 && d->K == 4 * d->Cin,
+                      "gcd_gemm_f16: upsample=2 (phase form) needs Cin %% 64 == 0 and K == 4*Cin (Cin=%d K=%d)",
+                      d->Cin, d->K);
+        GCD_CHECK_ARG(d->stride == 1 && d->Hi > 0 && d->Wi > 0 && d->Ho == 2 * d->Hi && d->Wo == 2 * d->Wi &&
+                          !d->asym_pad && d->M % (d->Ho * d->Wo) == 0,
+                      "gcd_gemm_f16: upsample=2 needs Ho=2Hi, Wo=2Wi, stride 1 and M = frames*Ho*Wo");
+        GCD_CHECK_ARG(d->Wi % 8 == 0, "gcd_gemm_f16: upsample=2 (phase form) needs Wi %% 8 == 0 (Wi=%d)", d->Wi);
+        GCD_CHECK_ARG(d->out_kind == GCD_OUT_F32 && !d->R1 && !d->R2 && !d->rowvec && !d->frame_alpha &&
+                          !d->operand_bf16,
+                      "gcd_gemm_f16: upsample=2 (phase form) writes fp32 rows + bias only: no residual, per-frame "
+                      "vector, blend, fp16 / GEGLU output or bf16 operands");
+        return 0;
+      }
       GCD_CHECK_ARG(d->Cin > 0 && d->Cin % 32 == 0 && d->K == 9 * d->Cin,
                     "gcd_gemm_f16: conv3x3 needs Cin %% 32 == 0 and K == 9*Cin (Cin=%d K=%d)",
                     d->Cin, d->K);
@@ -454,7 +480,7 @@ extern "C" int gcd_gemm_f16(const gcd_gemm_desc* d, void* stream) {
   const int impl = gcd_tune_get(GCD_TUNE_GEMM_IMPL);
   bool use_pp = false;
   if (impl != 1 && impl != 5 && impl != 6 && gcd_gemm_pp_supported(k, d->mode)) {
-    const int64_t tiles = (int64_t)((d->M + 255) / 256) * ((d->N + 319) / 320);
+    const int64_t tiles = pp_tiles(d);
     int min_tiles = gcd_tune_get(GCD_TUNE_PP_MIN_TILES);
     if (min_tiles <= 0) min_tiles = (d->sched & 2) ? 128 : 192;   // sched bit 1: the caller's shapes pay from 128 tiles
     use_pp = (impl >= 2 && impl != 7) || ((impl == 0 || impl == 7) && tiles >= min_tiles && d->N >= 160);
@@ -517,6 +543,16 @@ extern "C" int gcd_gemm_f16(const gcd_gemm_desc* d, void* stream) {
   // temporal descriptor must come back as an argument error, never reach a gather
   if (const int rc = validate_geometry(d)) return rc;
 
+  // The phase form of the x2 up-convolution exists on the 8-phase 256 x 320 tile kernel only: a shape or knob that
+  // would send it elsewhere (the general kernel, the ring kernel, split-K over few tiles) is an argument error.
+  if (d->mode == GCD_GEMM_CONV3X3 && d->upsample == 2) {
+    GCD_CHECK_ARG(use_pp && impl != 3 && gcd_gemm_p8_supported(k, d->mode),
+                  "gcd_gemm_f16: upsample=2 (phase form) needs the 8-phase 256x320 tile kernel, which the shape "
+                  "(%lld tiles: the automatic choice takes the general kernel or split-K) or GCD_TUNE_GEMM_IMPL=%d "
+                  "rules out", (long long)pp_tiles(d), impl);
+    return gcd_gemm_pp_launch(k, d->mode, s);
+  }
+
   // N == 16: the UNet's output head (320 -> 4, padded).  GCD_TUNE_GEMM_IMPL = 1 keeps it on the general kernel (tests).
   if (impl == 0 && gcd_conv3x3_narrow_supported(k, d->mode)) return gcd_conv3x3_narrow_launch(k, s);
 
@@ -563,7 +599,9 @@ extern "C" int gcd_gemm_colstats_supported(const gcd_gemm_desc* d) {
   if (d->mode != GCD_GEMM_PLAIN && (d->Cin <= 0 || d->Cin % 32 != 0)) return 0;
   const int impl = gcd_tune_get(GCD_TUNE_GEMM_IMPL);
   if (impl == 1 || impl == 5 || impl == 6) return 0;          // general kernel forced
-  const int64_t tiles = (int64_t)(d->M / 256) * (d->N / 320);
+  const bool up2 = d->mode == GCD_GEMM_CONV3X3 && d->upsample == 2;
+  if (up2 && (d->Cin % 64 != 0 || d->K != 4 * d->Cin || d->Wi % 8 != 0 || impl == 3)) return 0;
+  const int64_t tiles = up2 ? pp_tiles(d) : (int64_t)(d->M / 256) * (d->N / 320);
   int min_tiles = gcd_tune_get(GCD_TUNE_PP_MIN_TILES);
   if (min_tiles <= 0) min_tiles = (d->sched & 2) ? 128 : 192;
   if ((impl == 0 || impl == 7) && tiles < min_tiles) return 0;      // automatic choice: general kernel / split-K

@@ -92,6 +92,8 @@ __device__ __forceinline__ f32x4 gcd_load_res(const float* p) {
 // gemm_pp.hip: the 256 x 320 ping-pong kernel.
 bool gcd_gemm_pp_supported(const GemmK& k, int mode);
 int gcd_gemm_pp_launch(const GemmK& k, int mode, hipStream_t s);
+// gemm_p8.hip: shapes the 8-phase K loop on the same tile takes (the only home of the phase form, k.up == 2)
+bool gcd_gemm_p8_supported(const GemmK& k, int mode);
 
 // gemm_pp.hip: split-K launch = partial sums into `ws` + reduce-and-epilogue kernel.
 int gcd_gemm_pp_launch_splitk(const GemmK& k, int mode, int splitk, float* ws, hipStream_t s);

@@ -63,6 +63,15 @@ constexpr int P8_CONV_HALO = 3;
 constexpr int P8_PANEL = 288 * 128;                      // 36864: largest panel (four 64-pixel segments of 72 rows)
 constexpr int P8_HALO_W0 = 2 * P8_PANEL;                 // 73728: the two W K-tile buffers follow the two panels
 static_assert(P8_HALO_W0 + 2 * P8_W_BYTES <= P8_BIAS0, "halo layout must fit below the addend buffers");
+// MODE 4 (internal, gcd_gemm_desc.upsample == 2): the nearest-x2 up-convolution as four 2 x 2 PHASE convolutions in one
+// launch.  Output pixel (2i + py, 2j + px) sees only the input pixels (i + py - 1 + a, j + px - 1 + c), a, c in {0, 1}:
+// two of the three up-sampled rows / columns under a 3 x 3 window are the same input pixel, so the nine taps fold into
+// four (packing.pack_conv3x3_up_phases: W [4][N][4 Cin], phase ph = 2 py + px, K order (a, c, cin)) and K = 4 Cin.
+// A tile = (phase, 256 LOW-RES tokens, 320 channels): inside the kernel M counts low-res tokens (frames * Hi * Wi) and
+// tiles_m = 4 x the M-tiles of a phase, phase-minor — the four phases of an M-tile group are neighbours in the tile order
+// and read the same A rows.  The A walk is CONV3X3's with stride 1 and tap offsets (tap / 2 + py - 1, tap % 2 + px - 1);
+// the epilogue scatters tile row (n, i, j) to output row n Ho Wo + (2i + py) Wo + 2j + px.
+constexpr int P8_CONV_UP2 = 4;
 
 #define P8_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #define P8_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
@@ -72,6 +81,91 @@ static_assert(P8_HALO_W0 + 2 * P8_W_BYTES <= P8_BIAS0, "halo layout must fit bel
     __builtin_amdgcn_s_barrier();        \
     __builtin_amdgcn_sched_barrier(0);   \
   } while (0)
+
+// UP2 epilogue of a FULL 64 x 160 wave tile: gcd_epi_f32_rows_full without residuals, rows scattered to the pixels of
+// phase ph.  Wi % 8 == 0, so each of the 8 row groups a lane stores (tile rows rr + 8 k) lies inside one image row: the
+// output row of a group's first token is wave-uniform (scalar registers), the lane adds 2 rr rows.
+// STATS (Hi Wi % 64 == 0: the wave's 64 tokens lie in ONE frame): the [sum | sumsq] rows of these 64 output rows go to
+// block n Ho Wo / 64 + ph Hi Wi / 64 + (token within the frame) / 64 — frame n owns blocks [n Ho Wo / 64, (n + 1) Ho Wo / 64)
+// as in the row-ordered form, so gcd_groupnorm_stats_from_colsums reads them unchanged.
+template <bool STATS>
+__device__ __forceinline__ void p8_epi_up2_rows_full(const GemmK& p, GcdAcc16& acc, int m_base, int n_base, int lane,
+                                                     const float* lb, char* stage, int ph) {
+  const int rr = lane >> 3, cc = (lane & 7) * 4;
+  const int64_t col = n_base + cc;
+  const int py = ph >> 1, px = ph & 1;
+  const int hwi = p.Hi * p.Wi;
+  int64_t gbase[8];   // element offset of the output row of token m_base + 8 k (wave-uniform)
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int m = m_base + 8 * k;
+    const int fr = m / hwi, rem = m - fr * hwi;
+    const int i = rem / p.Wi, j0 = rem - i * p.Wi;
+    gbase[k] = (((int64_t)fr * p.Ho + 2 * i + py) * p.Wo + 2 * j0 + px) * p.ldo;
+  }
+  float* const op = (float*)p.out + (int64_t)(2 * rr) * p.ldo + col;
+  const char* const rd = stage + rr * GCD_EPI_ROW_F32 + cc * 4;
+  const float sa = p.s_acc;
+  f32x4 cs = {0.f, 0.f, 0.f, 0.f}, cq = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int b = 0; b < 10; ++b) {
+    const int i = b >> 1, j = b & 1;
+    gcd_stage_tile32(acc, i, j, stage, lane);
+    const f32x4 bv = *(const f32x4*)(lb + 32 * i + cc);
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      f32x4 v = *(const f32x4*)(rd + qq * 8 * GCD_EPI_ROW_F32);
+      v = (v + bv) * sa;
+      if (STATS) {
+        cs += v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) cq[e] = fmaf(v[e], v[e], cq[e]);
+      }
+      gcd_store16<(GCD_EPI_WT & 4) != 0, (GCD_EPI_NT & 4) != 0>(op + gbase[4 * j + qq] + 32 * i, v);
+    }
+    if (STATS && j == 1) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        cs[e] = gcd_sum_lane_bits_345(cs[e]);
+        cq[e] = gcd_sum_lane_bits_345(cq[e]);
+      }
+      if (rr == 0) {
+        const int fr = m_base / hwi;
+        const int64_t blk = (int64_t)fr * (4 * (hwi >> 6)) + ph * (hwi >> 6) + ((m_base - fr * hwi) >> 6);
+        float* dst = p.colstats + blk * 2 * p.N + col + 32 * i;
+        *(f32x4*)dst = cs;
+        *(f32x4*)(dst + p.N) = cq;
+      }
+      cs = f32x4{0.f, 0.f, 0.f, 0.f};
+      cq = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// UP2, ragged wave tiles (rows past the last low-res token, columns past N): direct stores from the accumulator layout
+__device__ __forceinline__ void p8_epi_up2_ragged(const GemmK& p, GcdAcc16& acc, int m_base, int n_base, int lane, int ph) {
+  const int r15 = lane & 15, q = lane >> 4;
+  const int py = ph >> 1, px = ph & 1;
+  const int hwi = p.Hi * p.Wi;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int m = m_base + 16 * t + r15;
+    if (m >= p.M) continue;
+    const int fr = m / hwi, rem = m - fr * hwi;
+    const int i = rem / p.Wi, j = rem - i * p.Wi;
+    float* const orow = (float*)p.out + (((int64_t)fr * p.Ho + 2 * i + py) * p.Wo + 2 * j + px) * p.ldo;
+#pragma unroll
+    for (int c = 0; c < 10; ++c) {
+      const int n = n_base + 16 * c + 4 * q;
+      if (n >= p.N) continue;
+      f32x4 v = acc[c][t];
+      if (p.bias) v += *(const f32x4*)(p.bias + n);
+      v *= p.s_acc;
+      *(f32x4*)(orow + n) = v;
+    }
+  }
+}
 
 // VAR bits: 2048 persistent (256 workgroups walk the tiles), 4096 per-64-row column statistics (gcd_gemm_desc.colstats),
 // 8192 bfloat16 operands (round 5: the fine-tune step's GEMMs in the type cfg4 names; fp32 outputs only),
@@ -106,6 +200,9 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const GemmK p) {
   constexpr bool READS_FIRST = (MODE == GCD_GEMM_PLAIN) != ((VAR & 16) != 0);
   constexpr bool SETPRIO = (MODE != GCD_GEMM_PLAIN) != ((VAR & 32) != 0);
   constexpr int GM = ((MODE == GCD_GEMM_PLAIN) != ((VAR & 64) != 0)) ? 8 : P8_GROUP_M;
+  constexpr bool UP2 = MODE == P8_CONV_UP2;                       // four 2 x 2 phase convolutions (see P8_CONV_UP2)
+  constexpr bool CONV = MODE == GCD_GEMM_CONV3X3 || UP2;          // the per-piece packed (frame, y, x0) A walk
+  static_assert(!UP2 || GM == 4, "UP2: a group of M-tiles in the tile order = the four phases of one low-res M-tile");
 
   // ---- XCD-aware, panel-sharing tile assignment (bijective for any grid; as gemm_pp.hip) ----
   int L, L_end, L_step;
@@ -121,6 +218,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const GemmK p) {
 
   // ---- per-tile state ----
   int m0 = 0, n0 = 0, kz = 0, s_begin = 0, nK = p.K >> 6;
+  int up_ph = 0;                                                 // UP2: the tile's phase 2 py + px (block-uniform)
   const int lrow = lane >> 3;
   const unsigned srcchunk = ((lane & 7) ^ (lane >> 3)) << 4;     // the 16-byte chunk of its row this lane fetches
   const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)p.a_bytes, 0x00020000);
@@ -180,16 +278,22 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const GemmK p) {
     for (int j = 0; j < 4; ++j) a_off[j] = halo_piece_off(j, kh);
   };
   auto unpack_set = [&](int r, int tap) {
-    if (MODE == GCD_GEMM_CONV3X3) {
+    if (CONV) {
       const unsigned pc = a_pc[r];
       const int x0 = pc & 2047, y = (pc >> 11) & 1023, fr = (int)(pc >> 21);
-      const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
+      const int dy = UP2 ? (tap >> 1) + (up_ph >> 1) - 1 : tap / 3 - 1;
+      const int dx = UP2 ? (tap & 1) + (up_ph & 1) - 1 : tap - (tap / 3) * 3 - 1;
       const unsigned ln = __lane_id();      // (re-derived here: nothing of this block stays live through the K loop)
       const int xv = x0 + (int)(ln >> 3);
       const unsigned sc = ((ln & 7) ^ (ln >> 3)) << 4;
       int iy, ix;
       bool row_ok, ok;
-      if (p.up) {
+      if (UP2) {   // (y, xv) are low-res coordinates; stride 1
+        iy = y + dy;
+        ix = xv + dx;
+        row_ok = iy >= 0 && iy < p.Hi;
+        ok = (unsigned)ix < (unsigned)p.Wi;
+      } else if (p.up) {
         const int uy = y + dy, ux = xv + dx;
         row_ok = uy >= 0 && uy < p.Ho;
         ok = (unsigned)ux < (unsigned)p.Wo;
@@ -240,6 +344,10 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const GemmK p) {
       tile_n = rem / gm;
       tile_m = m_first + rem - tile_n * gm;
     }
+    if (UP2) {
+      up_ph = tile_m & 3;
+      tile_m >>= 2;
+    }
     m0 = tile_m * P8_BM;
     n0 = tile_n * P8_BN;
     s_begin = 0;
@@ -276,13 +384,14 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const GemmK p) {
         const int g = 2 * wave + (r & 1);
         const int m = m0 + 64 * (g >> 2) + 32 * (r >> 1) + 8 * (g & 3) + lrow;
         if (MODE == GCD_GEMM_TEMPORAL3) a_pk[r] = ((unsigned)((m / p.HW) % p.T) << 26) | (unsigned)m;
-        if (MODE == GCD_GEMM_CONV3X3) {
+        if (CONV) {
           const int mp = m0 + 64 * (g >> 2) + 32 * (r >> 1) + 8 * (g & 3);     // first row of the piece: wave-uniform
-          const int hw = p.Ho * p.Wo;
+          const int pw = UP2 ? p.Wi : p.Wo;                                    // (UP2: rows are low-res tokens)
+          const int hw = (UP2 ? p.Hi : p.Ho) * pw;
           const int fr = mp / hw;          // fr >= a_frames for pieces past M: unpack_set marks them out of range
           const int rem = mp - fr * hw;
-          const int y = rem / p.Wo;
-          a_pc[r] = ((unsigned)fr << 21) | ((unsigned)y << 11) | (unsigned)(rem - y * p.Wo);
+          const int y = rem / pw;
+          a_pc[r] = ((unsigned)fr << 21) | ((unsigned)y << 11) | (unsigned)(rem - y * pw);
         }
       }
       const int k0 = s_begin * 64;
@@ -302,7 +411,8 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const GemmK p) {
         g = g < 20 ? g : 19;        // (the unused third slot of a 2-piece wave)
         const int row = 160 * (g / 10) + 80 * reg + 8 * (g % 10);
         w_row[reg][j] = row;
-        w_roff[reg][j] = (unsigned)(n0 + row) * (unsigned)p.K * 2u;
+        // (UP2: the phase's [N][K] slab; tile rows past N read the next phase's rows, whose columns no epilogue stores)
+        w_roff[reg][j] = (unsigned)((UP2 ? up_ph * p.N : 0) + n0 + row) * (unsigned)p.K * 2u;
       }
     if (!SPLITK) {
       const int m_last = min(m0 + P8_BM, p.M) - 1;
@@ -668,6 +778,14 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const GemmK p) {
         GemmK q = p;
         q.out = (float*)p.out + (int64_t)e_kz * p.split_stride;
         gcd_epilogue_64x160(q, acc, wm_base, wn_base, elane);
+      } else if constexpr (UP2) {
+        // fp32 rows + bias, scattered to the phase's pixels.  STATS launches (gcd_gemm_f16 validated N % 320 == 0 and
+        // Hi Wi % 64 == 0) have wave tiles that are full or entirely past the last token.
+        if (wm_base + 64 <= p.M && wn_base + 160 <= p.N) {
+          p8_epi_up2_rows_full<STATS>(p, acc, wm_base, wn_base, elane, e_bias + 160 * wn, e_stage, up_ph);
+        } else if (!STATS) {
+          p8_epi_up2_ragged(p, acc, wm_base, wn_base, elane, up_ph);
+        }
       } else if constexpr (STATS) {
         // fp32 rows + per-64-row column statistics for the next GroupNorm (gcd_gemm_desc.colstats): gcd_gemm_f16
         // validated that EVERY tile of the launch is full, has tile-uniform per-frame vectors / blend factors and at
@@ -759,7 +877,7 @@ template <int MODE>
 void p8_extents(GemmK& kk) {
   int64_t rows = kk.M, width = kk.K;
   kk.a_frames = 0;
-  if (MODE == GCD_GEMM_CONV3X3 || MODE == P8_CONV_HALO) {
+  if (MODE == GCD_GEMM_CONV3X3 || MODE == P8_CONV_HALO || MODE == P8_CONV_UP2) {
     kk.a_frames = kk.M / (kk.Ho * kk.Wo);
     rows = (int64_t)kk.a_frames * kk.Hi * kk.Wi;
     width = kk.Cin;
@@ -767,7 +885,7 @@ void p8_extents(GemmK& kk) {
     width = kk.Cin;
   }
   kk.a_bytes = (uint32_t)(((rows - 1) * kk.lda + width) * 2);
-  kk.w_bytes = (uint32_t)((int64_t)kk.N * kk.K * 2);
+  kk.w_bytes = (uint32_t)((int64_t)kk.N * kk.K * 2 * (MODE == P8_CONV_UP2 ? 4 : 1));
 }
 
 template <int MODE, int VAR = 0, int EPI = 0>
@@ -778,6 +896,10 @@ int launch_p8(const GemmK& k, hipStream_t s) {
   GemmK kk = k;
   p8_extents<MODE>(kk);
   kk.tiles_m = (k.M + P8_BM - 1) / P8_BM;
+  if (MODE == P8_CONV_UP2) {   // kernel-side M = low-res tokens; four phase tiles per 256 of them
+    kk.M = kk.a_frames * k.Hi * k.Wi;
+    kk.tiles_m = 4 * ((kk.M + P8_BM - 1) / P8_BM);
+  }
   kk.tiles_n = (k.N + P8_BN - 1) / P8_BN;
   int64_t nblk = (int64_t)kk.tiles_m * kk.tiles_n;
   GCD_CHECK_ARG(nblk > 0 && nblk < (1ll << 31), "gcd_gemm_f16 (p8): bad grid %lld", (long long)nblk);
@@ -824,11 +946,14 @@ bool gcd_gemm_p8_supported(const GemmK& k, int mode) {
   // below the out-of-range marker
   const int64_t a_rows = mode == GCD_GEMM_CONV3X3 ? (int64_t)(k.M / ((int64_t)k.Ho * k.Wo)) * k.Hi * k.Wi : (int64_t)k.M;
   if ((a_rows + 256 + (mode == GCD_GEMM_TEMPORAL3 ? k.HW : 0)) * k.lda * 2 + (int64_t)k.K * 2 >= 0xFFFFFF00ll) return false;
-  if (((int64_t)k.N + 320) * k.K * 2 >= 0xFFFFFF00ll) return false;
+  if (((int64_t)k.N * (k.up == 2 ? 4 : 1) + 320) * k.K * 2 >= 0xFFFFFF00ll) return false;
   if (k.out_kind == GCD_OUT_GEGLU && k.N % 32 != 0) return false;
   if (mode == GCD_GEMM_CONV3X3) {   // a piece = 8 consecutive x of one image row; packed (frame, y, x0): 11 + 10 + 11 bits
     const int64_t frames = (int64_t)k.M / ((int64_t)k.Ho * k.Wo);
     if (k.Wo % 8 != 0 || k.Ho > 1024 || k.Wo > 2048 || frames > 2046) return false;
+    // the phase form (upsample == 2): pieces are 8 consecutive x of a LOW-RES row; fp32 rows + bias only, fp16 operands
+    if (k.up == 2 && (k.Wi % 8 != 0 || k.out_kind != GCD_OUT_F32 || k.R1 || k.R2 || k.rowvec || k.frame_alpha || k.operand_bf16))
+      return false;
   }
   if (mode == GCD_GEMM_TEMPORAL3 && (k.M + 256 >= (1 << 26) || k.T > 31)) return false;
   return true;
@@ -887,6 +1012,8 @@ int gcd_gemm_p8_launch(const GemmK& k, int mode, bool persist, hipStream_t s) {
     }
   }
 #endif
+  if (mode == GCD_GEMM_CONV3X3 && k.up == 2)   // gcd_gemm_p8_supported: fp32 rows + bias
+    return k.colstats ? launch_p8<P8_CONV_UP2, 2048 + 4096, 3>(k, s) : launch_p8<P8_CONV_UP2, 2048, 3>(k, s);
   if (k.operand_bf16) {   // gcd_gemm_p8_supported: fp32 rows, at most the first residual, no colstats
     switch (mode) {
       case GCD_GEMM_PLAIN:

@@ -46,6 +46,10 @@ _GN_REVERSE = os.environ.get("GCD_GN_REVERSE", "1") != "0"   # A/B switch (see o
 # 1: 101.84, 2: 101.76 / 100.57, 3: 101.97, 4: 102.04 — 2 is the default (-0.3 ms; the cache keeps less of a producer's
 # tail than its size suggests, the rest of the step's traffic flows through it too).
 _ZIGZAG = int(os.environ.get("GCD_ZIGZAG", "2"))
+# The x2 up-convolutions as four 2 x 2 phase convolutions in one launch (gcd_gemm_desc.upsample = 2: 4/9 of the
+# FLOPs of the gathered 3 x 3 form) wherever `ops.up_phases_ok` holds.  GCD_UP_PHASES=0 restores the 3 x 3 form
+# everywhere (A/B switch; the two forms round their weights differently, so results differ at the 2e-4 level).
+_UP_PHASES = os.environ.get("GCD_UP_PHASES", "1") != "0"
 _ITEMSIZE = {torch.float16: 2, torch.float32: 4, torch.float64: 8, torch.uint8: 1}
 
 
@@ -286,8 +290,14 @@ class UNetEngine:
                     layers.append(dict(kind="down", w=packing.pack_conv3x3(m.op.weight), b=_f32(m.op.bias),
                                        cin=m.channels, cout=m.out_channels))
                 elif isinstance(m, Upsample):
-                    layers.append(dict(kind="up", w=packing.pack_conv3x3(m.conv.weight), b=_f32(m.conv.bias),
-                                       cin=m.channels, cout=m.out_channels))
+                    d = dict(kind="up", b=_f32(m.conv.bias), cin=m.channels, cout=m.out_channels)
+                    if _UP_PHASES and m.channels % 64 == 0:
+                        # the phase form's [4, Cout, 4 Cin]; the nine-tap copy is not kept: `_upsample` packs it from
+                        # the parameter the first time a shape cannot take the phase form (`ops.up_phases_ok`)
+                        d["wp"], d["w"], d["w_src"] = packing.pack_conv3x3_up_phases(m.conv.weight), None, m.conv.weight
+                    else:
+                        d["w"] = packing.pack_conv3x3(m.conv.weight)
+                    layers.append(d)
                 elif isinstance(m, torch.nn.Conv2d):
                     layers.append(dict(kind="conv_in", w=packing.pack_conv3x3(m.weight, cin_pad=CIN_PAD),
                                        b=_f32(m.bias), cout=m.out_channels))
@@ -367,7 +377,7 @@ class UNetEngine:
         travel with `out` (Workspace.attach); otherwise any stale sums of `out` are dropped."""
         ws = self.ws
         if ops.gemm(a16, w16, out, probe_colstats=True, **kw):
-            cs = ws.alloc((2 * (kw["M"] // 64), w16.shape[0]), torch.float32)
+            cs = ws.alloc((2 * (kw["M"] // 64), w16.shape[-2]), torch.float32)
             self._gemm(a16, w16, out, colstats=cs, **kw)
             ws.attach(out, cs)
         else:
@@ -397,7 +407,7 @@ class UNetEngine:
             # only the 256 x 320 tile kernels honour the bit (automatic choice: >= 192 tiles and N >= 160, gemm.hip); a
             # small launch on the general kernel walks front to back whatever it is told and must not flip the record
             # the next big launch alternates against
-            M, N = kw["M"], w16.shape[0]
+            M, N = kw["M"], w16.shape[-2]
             if ((M + 255) // 256) * ((N + 319) // 320) >= 192 and N >= 160:
                 kw["sched"] = self._next_dir()
         return ops.gemm(a16, w16, out, **kw)
@@ -832,8 +842,14 @@ class UNetEngine:
         ops.cast_f16(h, a16)
         ws.release(h)
         out = ws.alloc((N * Ho * Wo, L["cout"]), torch.float32)
-        self._gemm_gn(a16, L["w"], out, M=N * Ho * Wo, mode=GEMM_CONV3X3, bias=L["b"],
-                      conv=dict(Cin=L["cin"], Hi=H, Wi=W, Ho=Ho, Wo=Wo, stride=1, upsample=1))
+        if L.get("wp") is not None and ops.up_phases_ok(N, H, W, L["cin"], L["cout"]):
+            w, up = L["wp"], 2
+        else:
+            if L["w"] is None:
+                L["w"] = packing.pack_conv3x3(L["w_src"])
+            w, up = L["w"], 1
+        self._gemm_gn(a16, w, out, M=N * Ho * Wo, mode=GEMM_CONV3X3, bias=L["b"],
+                      conv=dict(Cin=L["cin"], Hi=H, Wi=W, Ho=Ho, Wo=Wo, stride=1, upsample=up))
         ws.release(a16)
         st["H"], st["W"] = Ho, Wo
         return out

@@ -61,10 +61,31 @@ class _Timed:
 TUNE_GEMM_IMPL, TUNE_ATTN_IMPL = 0, 1
 
 
+TUNE_PP_MIN_TILES = 2
+# what the library's knobs hold, as far as this process can know: their environment defaults + every tune_set since
+_tune = {TUNE_GEMM_IMPL: int(os.environ.get("GCD_GEMM_IMPL", "0") or 0),
+         TUNE_PP_MIN_TILES: int(os.environ.get("GCD_PP_MIN_TILES", "0") or 0)}
+
+
 def tune_set(knob: int, value: int) -> None:
     """Kernel-selection knob of libgcd_amd (gcd_tune_set): used by the tests to force every GEMM
     kernel over the same cases, and by the A/B tools."""
     check(_lib.load().gcd_tune_set(knob, value), "gcd_tune_set")
+    _tune[knob] = value
+
+
+def up_phases_ok(frames: int, Hi: int, Wi: int, Cin: int, N: int) -> bool:
+    """Would gcd_gemm_f16 take the phase form (upsample = 2) of an x2 up-convolution of this shape?  Mirrors its rule
+    (gemm.hip): Wi % 8 == 0, Cin % 64 == 0, and a kernel choice that lands on the 8-phase 256 x 320 tile kernel — forced
+    (GCD_TUNE_GEMM_IMPL 2 / 4), or automatic from 192 tiles of (phase, 256 low-res tokens, 320 channels) and N >= 160.
+    A disagreement is loud: the library refuses the descriptor, it has no other kernel for this form."""
+    if Wi % 8 or Cin % 64 or N % 16:
+        return False
+    impl = _tune.get(TUNE_GEMM_IMPL, 0)
+    if impl not in (0, 7):
+        return impl >= 2 and impl not in (3, 5, 6)     # forced: every tile-kernel value but the ring kernel's
+    tiles = 4 * ((frames * Hi * Wi + 255) // 256) * ((N + 319) // 320)
+    return tiles >= (_tune.get(TUNE_PP_MIN_TILES, 0) or 192) and N >= 160
 
 
 def _need_gpu(*ts) -> None:
@@ -139,6 +160,8 @@ def gemm(a16: torch.Tensor, w16: torch.Tensor, out: torch.Tensor, *, M: int, mod
 
     conv: dict(Cin, Hi, Wi, Ho, Wo, stride, upsample) for GEMM_CONV3X3 or dict(Cin, T, HW) for
     GEMM_TEMPORAL3.  a16 is the token-major fp16 activation [rows, Cin].
+    upsample = 2 is the phase form of the x2 up-convolution: w16 is packing.pack_conv3x3_up_phases' [4, N, 4*Cin]
+    (see `up_phases_ok`; M stays frames * Ho * Wo).
     colstats: optional fp32 [2 * M / 64, N] that receives the per-64-row column sums / sums of squares
     of the fp32 output (gcd_gemm_desc.colstats) for `groupnorm_stats_from_colsums`.
     probe_colstats: do not launch; return whether `colstats` would be honoured for this call.
@@ -147,7 +170,11 @@ def gemm(a16: torch.Tensor, w16: torch.Tensor, out: torch.Tensor, *, M: int, mod
     _need_gpu(a16, w16, out)
     want = torch.bfloat16 if operand_bf16 else torch.float16
     assert a16.dtype == want and w16.dtype == want, f"operands must be {want}"
-    N, K = w16.shape
+    if mode == GEMM_CONV3X3 and int((conv or {}).get("upsample", 0)) == 2:
+        assert w16.dim() == 3 and w16.shape[0] == 4 and w16.is_contiguous(), "upsample=2 takes phase weights [4, N, 4*Cin]"
+        N, K = w16.shape[1:]
+    else:
+        N, K = w16.shape
     d = GemmDesc()
     d.A, d.W, d.out = a16.data_ptr(), w16.data_ptr(), out.data_ptr()
     d.lda, d.ldo = _ld(a16), _ld(out)      # (ignored for a tile-blocked operand / output)

@@ -30,6 +30,35 @@ def pack_conv3x3(w: torch.Tensor, cin_pad: int = 0, cout_pad: int = 0,
     return out.reshape(cout_p, 9 * cin_p).contiguous()
 
 
+# kh (or kw) taps that fall on the same input row for output parity p and phase tap a: S[p][a]
+_UP_PHASE_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def pack_conv3x3_up_phases(w: torch.Tensor) -> torch.Tensor:
+    """nn.Conv2d weight [Cout, Cin, 3, 3] of an `Upsample` (nearest x2, then the conv) -> fp16 [4, Cout, 4*Cin]: the
+    four 2 x 2 phase convolutions on the LOW-RES input that compute the same thing (gcd_gemm_desc.upsample = 2).
+
+    out[2i+py, 2j+px] = b + sum_{a,c in {0,1}} Wp[2py+px][a][c] . x[i+py-1+a, j+px-1+c]   (x = 0 outside the image):
+    tap kh reads up-sampled row 2i+py-1+kh = input row i-1, i, i (py = 0) or i, i, i+1 (py = 1), so Wp[..][a][..] sums
+    W over kh in S[py][a], S[0] = ({0}, {1, 2}), S[1] = ({0, 1}, {2}); the same for kw with px, c.  K order (a, c, cin).
+    The sums are formed in fp32 from the fp32 parameter and rounded to fp16 once.
+    """
+    cout, cin, kh, kw = w.shape
+    assert (kh, kw) == (3, 3)
+    w32 = w.detach().to(torch.float32)
+    out = torch.empty(4, cout, 2, 2, cin, dtype=torch.float32, device=w.device)
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for c in range(2):
+                    acc = None
+                    for i in _UP_PHASE_TAPS[py][a]:
+                        for j in _UP_PHASE_TAPS[px][c]:
+                            acc = w32[:, :, i, j] if acc is None else acc + w32[:, :, i, j]
+                    out[2 * py + px, :, a, c, :] = acc
+    return out.reshape(4, cout, 4 * cin).to(torch.float16).contiguous()
+
+
 def pack_conv1x1(w: torch.Tensor) -> torch.Tensor:
     """nn.Conv2d 1x1 weight [Cout, Cin, 1, 1] -> fp16 [Cout, Cin]."""
     return w.detach().reshape(w.shape[0], w.shape[1]).to(torch.float16).contiguous()

@@ -87,6 +87,16 @@ typedef struct gcd_gemm_desc {
   int32_t Ho, Wo;    /* output spatial size                       */
   int32_t stride;    /* 1 or 2 (CONV3X3)                          */
   int32_t upsample;  /* 1: nearest x2 upsample fused before conv  */
+                     /* 2: the same convolution as four 2 x 2 PHASE convolutions on the low-res input, one launch:
+                           out[2i+py, 2j+px] = b + sum_{a,c in {0,1}} Wp[2py+px][a][c] . x[i+py-1+a, j+px-1+c], zero
+                           outside the image.  W = [4][N][4*Cin] fp16, phase-major, K order (a, c, cin), K = 4*Cin
+                           (packing.pack_conv3x3_up_phases folds the nine taps in fp32: 4/9 of the FLOPs of value 1).
+                           M stays frames*Ho*Wo, out / colstats keep their meaning (colstats: Hi*Wi % 64 == 0,
+                           N % 320 == 0; the blocks of a frame are written in phase order, which no consumer sees).
+                           Needs Cin % 64 == 0, Wi % 8 == 0, stride 1, fp32 output, bias as the only epilogue input, and
+                           a kernel choice that lands on the 8-phase 256x320 tile kernel without split-K (automatic:
+                           from 192 tiles of (phase, 256 low-res tokens, 320 channels)); anything else is an argument
+                           error, there is no other kernel for this form.                                       */
   int32_t T;         /* frames per clip (TEMPORAL3)               */
   int32_t HW;        /* pixels per frame (TEMPORAL3)              */
   /* epilogue: out = s_acc[frame] * (acc + bias[n] + rowvec[m / rows_per_vec][n])
