@@ -3,7 +3,7 @@ weights of variance 1 / fan_in, under which no fp16 operand of the HIP path come
 Here the UNMODIFIED reference VideoUNet (oracle/ref_shim.py) runs the TINY width with
   * Student-t (nu = 3) weights — single weights tens of sigma out (oracle/weights.synth_tensor_heavy), and
   * the GEGLU projections scaled by GEGLU_GAIN so that the hidden tensor value * gelu(gate) — which the HIP path
-    stores in fp16 (clamped to the fp16 range in the epilogue) — reaches thousands,
+    stores in fp16 (a plain conversion in the epilogue: not clamped, inf above the fp16 range) — reaches thousands,
 and the fixture records, beside the output and the per-block taps, the largest |hidden| the reference saw in any GEGLU
 (forward hook on sgm.modules.attention.GEGLU, attention.py:87-94) so that the test can state how close to 65504 the
 case sits.  tests/test_unet_gpu.py::test_unet_forward_heavy_tailed_weights_vs_reference_golden holds the HIP path to
