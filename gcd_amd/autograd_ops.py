@@ -11,6 +11,9 @@ Conventions
   * `Fused` is ONE node for [LayerNorm | GroupNorm(+SiLU) | GEGLU ->] Linear / q|k|v / Conv3x3 / Conv (3,1,1)
     [+ per-frame vector] [+ residual]: the prologue writes the 16-bit GEMM operand directly, the epilogue terms ride
     in the GEMM as in the inference engine;
+  * the fused node and the attention cores are pairs of plain functions that state their inputs (`fused_forward` /
+    `fused_backward`, `spatial_` / `temporal_attention_forward` / `_backward`): `Fused`, `SpatialAttention` and
+    `TemporalAttention` adapt them to torch's tape, the planned engine (train_plan.py) calls them directly;
   * backward contractions reuse `gcd_gemm_f16`: dX of a Linear = dY @ W (W^T packed once per parameter version), dX of
     a stride-1 convolution = the forward implicit-GEMM convolution on dY with mirrored taps (no col2im), dW = dY^T @ X
     with both operands transposed by the vector transpose kernel and the GEMM split up to 32 ways along the token
@@ -25,6 +28,7 @@ torch.autograd over the CPU oracle, and the full-width step at cfg4's shape vs t
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import weakref
@@ -83,15 +87,23 @@ def set_deterministic(on: bool) -> None:
     DETERMINISTIC = on
 
 
-def _det_call(name: str, scratch_floats: int, device, call) -> None:
-    """One deterministic entry: `call(lib, scratch_ptr, scratch_floats)`; the partial sums live in the training workspace
-    (one per device and stream, consumed by the entry's own fold before anything else on that stream runs)."""
+def _reduction(default, det: str, scratch_floats, device, args) -> None:
+    """One of those five sums, its argument list `args` stated once for both modes.
+    default = (load, check, name): `name(*args, stream)` of the library `load()` returns.  DETERMINISTIC: the entry `det`
+    of the training library takes the same list with (scratch, scratch_floats) in front of the stream — the partial sums
+    live in the training workspace (one per device and stream, consumed by the entry's own fold before anything else on
+    that stream runs), which must hold the `scratch_floats(lib)` floats the entry needs."""
+    if not DETERMINISTIC:
+        load, chk, name = default
+        chk(getattr(load(), name)(*args, _stream()), name)
+        return
     lib = _lib.load_train()
     ws = _train_ws(device)
-    if scratch_floats > ws.numel():
-        raise _lib.GcdError(f"{name}: needs {scratch_floats} floats of scratch, the training workspace holds {ws.numel()}")
-    DET_CALLS[name] = DET_CALLS.get(name, 0) + 1
-    _lib.check_train(call(lib, ws.data_ptr(), ws.numel()), name)
+    need = int(scratch_floats(lib))
+    if need > ws.numel():
+        raise _lib.GcdError(f"{det}: needs {need} floats of scratch, the training workspace holds {ws.numel()}")
+    DET_CALLS[det] = DET_CALLS.get(det, 0) + 1
+    _lib.check_train(getattr(lib, det)(*args, ws.data_ptr(), ws.numel(), _stream()), det)
 
 
 def _dt(name: str) -> torch.dtype:
@@ -164,38 +176,23 @@ def set_wgrad_impl(name: str) -> None:
 set_wgrad_impl(os.environ.get("GCD_TRAIN_WGRAD", "tr"))     # a typo in the variable raises at import, it does not pick a path
 
 
-# The planned engine (gcd_amd/train_plan.py) sets this to an object with `grad_dest(param) -> fp32 tensor of the parameter's
-# shape | None` and `accumulate`: weight gradients are then written by the kernel STRAIGHT into that tensor, in the
-# parameter's own layout (gcd_wgrad_tr_f16_ex) — no padded temporary, no permuted copy.  None on the autograd path.
-# Round 6: not a module global any more.  The sink (and the fp16 pass-through switch below) live in a per-THREAD scope that a
-# plan opens around the operator calls of ITS OWN backward / forward (`grad_sink(plan)`, `f16_passthrough(True)`): two plans,
-# two host threads (one per GPU) or a DDP listener that re-enters the operators cannot see each other's setting.
+# `sink`, an ARGUMENT of the backward helpers below: the planned engine (gcd_amd/train_plan.py) passes its plan, an object
+# with `grad_dest(param) -> fp32 tensor of the parameter's shape | None`, `zeros(m, n)` and `accumulate`: weight gradients
+# are then written by the kernel STRAIGHT into that tensor, in the parameter's own layout (gcd_wgrad_tr_f16_ex) — no padded
+# temporary, no permuted copy.  None on the autograd path.  A plan hands itself to the operator calls of ITS OWN backward,
+# so two plans, two host threads (one per GPU) or a DDP listener that re-enters the operators cannot see each other's.
+# What is left in the per-THREAD scope is the tape engine's fp16 pass-through switch (`f16_passthrough`, further down).
 import contextlib as _contextlib
 import threading as _threading
 
 _SCOPE = _threading.local()
 
 
-def _sink():
-    return getattr(_SCOPE, "sink", None)
-
-
-@_contextlib.contextmanager
-def grad_sink(plan):
-    old = getattr(_SCOPE, "sink", None)
-    _SCOPE.sink = plan
-    try:
-        yield plan
-    finally:
-        _SCOPE.sink = old
-
-
-def _sink_dest(*params):
+def _sink_dest(sink, *params):
     """The flat-buffer destination of one parameter, or of several that lie back to back in it (q | k | v)."""
-    _GRAD_SINK = _sink()
-    if _GRAD_SINK is None:
+    if sink is None:
         return None
-    ds = [_GRAD_SINK.grad_dest(p) for p in params]
+    ds = [sink.grad_dest(p) for p in params]
     if any(d is None for d in ds):
         return None
     for a, b in zip(ds, ds[1:]):
@@ -205,10 +202,11 @@ def _sink_dest(*params):
 
 
 def _wgrad(dy16: torch.Tensor, x16: torch.Tensor, dest: Optional[torch.Tensor] = None, taps: int = 1,
-           n_real: Optional[int] = None, c_real: Optional[int] = None) -> torch.Tensor:
+           n_real: Optional[int] = None, c_real: Optional[int] = None, *, accumulate: bool = False) -> torch.Tensor:
     """dW [N, K] fp32 = dY^T X for dy16 [M, N], x16 [M, K] (same 16-bit type, rows = tokens).
     dest (planned engine): write into this tensor instead — element [n][c][tap] of a parameter [n_real][c_real][taps],
-    column k = tap * (K / taps) + c of the contraction (cropped to the real rows / channels); returns dest."""
+    column k = tap * (K / taps) + c of the contraction (cropped to the real rows / channels), added onto what is there
+    when `accumulate`; returns dest."""
     M, N = dy16.shape
     K = x16.shape[1]
     tr_ok = N % 8 == 0 and K % 8 == 0 and dy16.stride(1) == 1 and x16.stride(1) == 1 and \
@@ -221,7 +219,7 @@ def _wgrad(dy16: torch.Tensor, x16: torch.Tensor, dest: Optional[torch.Tensor] =
             scratch = torch.empty(int(lib.gcd_wgrad_tr_scratch_floats(M, N, K)), dtype=_f32, device=dy16.device)
             _lib.check_train(lib.gcd_wgrad_tr_f16_ex(
                 dy16.data_ptr(), dy16.stride(0), x16.data_ptr(), x16.stride(0), M, N, K, int(dy16.dtype == _bf16),
-                dest.data_ptr(), c_real, taps, n_real, c_real, int(bool(_sink() is not None and _sink().accumulate)),
+                dest.data_ptr(), c_real, taps, n_real, c_real, int(accumulate),
                 scratch.data_ptr(), scratch.numel(), _stream()), "gcd_wgrad_tr_f16_ex")
             return dest
     dw = torch.empty(N, K, dtype=_f32, device=dy16.device)
@@ -239,7 +237,7 @@ WGRAD_IMPLICIT = os.environ.get("GCD_TRAIN_WGRAD_IMPLICIT", "1") != "0"
 
 
 def _wgrad_conv(dy16: torch.Tensor, x16: torch.Tensor, dest: torch.Tensor, conv: int, n_real: int, c_real: int,
-                Ho: int = 0, Wo: int = 0, T: int = 0, HW: int = 0) -> torch.Tensor:
+                Ho: int = 0, Wo: int = 0, T: int = 0, HW: int = 0, *, accumulate: bool = False) -> torch.Tensor:
     """Weight gradient of a stride-1 3x3 convolution (conv = 1) or the (3,1,1) temporal convolution (conv = 2) straight into
     `dest` (the parameter's [Cout, Cin, taps...] slot): x16 [M, Cp] is the convolution's input operand, dy16 [M, N]."""
     M, N = dy16.shape
@@ -249,8 +247,8 @@ def _wgrad_conv(dy16: torch.Tensor, x16: torch.Tensor, dest: torch.Tensor, conv:
     scratch = torch.empty(int(lib.gcd_wgrad_tr_scratch_floats(M, N, taps * Cp)), dtype=_f32, device=dy16.device)
     _lib.check_train(lib.gcd_wgrad_conv_tr_f16(
         dy16.data_ptr(), dy16.stride(0), x16.data_ptr(), x16.stride(0), M, N, Cp, conv, Ho, Wo, T, HW,
-        int(dy16.dtype == _bf16), dest.data_ptr(), n_real, c_real,
-        int(bool(_sink() is not None and _sink().accumulate)), scratch.data_ptr(), scratch.numel(), _stream()),
+        int(dy16.dtype == _bf16), dest.data_ptr(), n_real, c_real, int(accumulate), scratch.data_ptr(), scratch.numel(),
+        _stream()),
         "gcd_wgrad_conv_tr_f16")
     return dest
 
@@ -288,32 +286,28 @@ def _gemm(a16, w16, out, **kw):
     return ops.gemm(a16, w16, out, operand_bf16=a16.dtype == _bf16, workspace=_train_ws(a16.device), sched=2, **kw)
 
 
-def _cast16_colsum(dy32: torch.Tensor, dtype: torch.dtype, rows_per_block: Optional[int], out_sums=None, total=None):
+def _cast16_colsum(dy32: torch.Tensor, dtype: torch.dtype, rows_per_block: Optional[int], out_sums=None, total=None, *,
+                   sink=None):
     """(dy16, sums [M / rows, N]): the incoming gradient rounded for the GEMMs and its row-block column sums (bias /
     per-frame-vector gradients) in one pass (gcd_cast_colsum_f32); plain cast when no sums are wanted or the width
     is not a multiple of 8."""
     M, N = dy32.shape
     if rows_per_block is None or N % 8:
-        return _cast16(dy32, dtype), (None if rows_per_block is None else _colsum(dy32, rows_per_block))
+        return _cast16(dy32, dtype), (None if rows_per_block is None else _colsum(dy32, rows_per_block, sink=sink))
     y = torch.empty(M, N, dtype=dtype, device=dy32.device)
     # out_sums (planned engine): the bias's own slot of the flat gradient buffer, zeroed once per step — the kernel's
     # atomics land there directly (no fill, no copy)
-    sums = out_sums if out_sums is not None else _zeros(M // rows_per_block, N, dy32.device)
+    sums = out_sums if out_sums is not None else _zeros(M // rows_per_block, N, dy32.device, sink)
     # total (planned engine): the bias's slot, receiving the sum over all row blocks in the same pass
-    if DETERMINISTIC:
-        _det_call("gcd_cast_colsum_det_f32",
-                  int(_lib.load_train().gcd_cast_colsum_det_scratch_floats(M, N, rows_per_block)), dy32.device,
-                  lambda lib, sp, sn: lib.gcd_cast_colsum_det_f32(
-                      dy32.data_ptr(), _ld(dy32), y.data_ptr(), _ld(y), M, N, rows_per_block, sums.data_ptr(),
-                      int(dtype == _bf16), 0 if total is None else total.data_ptr(), sp, sn, _stream()))
-        return y, sums
-    check(_lib.load().gcd_cast_colsum_f32(dy32.data_ptr(), _ld(dy32), y.data_ptr(), _ld(y), M, N, rows_per_block,
-                                          sums.data_ptr(), int(dtype == _bf16), 0 if total is None else total.data_ptr(),
-                                          _stream()), "gcd_cast_colsum_f32")
+    _reduction((_lib.load, check, "gcd_cast_colsum_f32"), "gcd_cast_colsum_det_f32",
+               lambda lib: lib.gcd_cast_colsum_det_scratch_floats(M, N, rows_per_block), dy32.device,
+               (dy32.data_ptr(), _ld(dy32), y.data_ptr(), _ld(y), M, N, rows_per_block, sums.data_ptr(), int(dtype == _bf16),
+                0 if total is None else total.data_ptr()))
     return y, sums
 
 
-def _grad_contractions(dy32: torch.Tensor, x16: torch.Tensor, w_t16, need_dx: bool, need_dw: bool, dy16=None, dw_dest=None):
+def _grad_contractions(dy32: torch.Tensor, x16: torch.Tensor, w_t16, need_dx: bool, need_dw: bool, dy16=None, dw_dest=None,
+                       *, accumulate: bool = False):
     """The two contractions every Linear-shaped backward needs, on gcd_gemm_f16:
          dX [M, K] = dY [M, N] @ W [N, K]      (w_t16() -> W^T, [K, N], in the backward operand type)
          dW [N, K] = dY^T [N, M] @ X [M, K]    (x16 [M, K]; split-K over the tokens)
@@ -338,31 +332,27 @@ def _grad_contractions(dy32: torch.Tensor, x16: torch.Tensor, w_t16, need_dx: bo
             wtp[:, :N] = wt
             _gemm(dyp, wtp, dx, M=M)
     if need_dw:
-        dw = _wgrad(dy16, _as_dtype(x16, dt), dest=dw_dest)
+        dw = _wgrad(dy16, _as_dtype(x16, dt), dest=dw_dest, accumulate=accumulate)
     return dx, dw
 
 
-def _zeros(m: int, n: int, device) -> torch.Tensor:
-    """A zeroed fp32 [m, n] accumulator: from the planned engine's per-step arena (one memset per step) when it runs,
+def _zeros(m: int, n: int, device, sink=None) -> torch.Tensor:
+    """A zeroed fp32 [m, n] accumulator: from the per-step arena of the planned engine's `sink` (one memset per step),
     else a fresh torch.zeros (one fill launch each)."""
-    if _sink() is not None:
-        z = _sink().zeros(m, n)
+    if sink is not None:
+        z = sink.zeros(m, n)
         if z is not None:
             return z
     return torch.zeros(m, n, dtype=_f32, device=device)
 
 
-def _colsum(x32: torch.Tensor, rows_per_block: Optional[int] = None) -> torch.Tensor:
+def _colsum(x32: torch.Tensor, rows_per_block: Optional[int] = None, *, sink=None) -> torch.Tensor:
     M, N = x32.shape
     rows = M if rows_per_block is None else rows_per_block
-    out = _zeros(M // rows, N, x32.device)
-    if DETERMINISTIC:
-        _det_call("gcd_rowblock_sum_det_f32", int(_lib.load_train().gcd_rowblock_sum_det_scratch_floats(M, N, rows)),
-                  x32.device, lambda lib, sp, sn: lib.gcd_rowblock_sum_det_f32(
-                      x32.data_ptr(), _ld(x32), M, N, rows, out.data_ptr(), sp, sn, _stream()))
-        return out
-    check(_lib.load().gcd_rowblock_sum_f32(x32.data_ptr(), _ld(x32), M, N, rows, out.data_ptr(), _stream()),
-          "gcd_rowblock_sum_f32")
+    out = _zeros(M // rows, N, x32.device, sink)
+    _reduction((_lib.load, check, "gcd_rowblock_sum_f32"), "gcd_rowblock_sum_det_f32",
+               lambda lib: lib.gcd_rowblock_sum_det_scratch_floats(M, N, rows), x32.device,
+               (x32.data_ptr(), _ld(x32), M, N, rows, out.data_ptr()))
     return out
 
 
@@ -543,36 +533,39 @@ def _contract_fwd(kind, a16, params, geo, bias_vec_res):
     raise ValueError(kind)
 
 
-def _contract_bwd(kind, dy, a16, params, geo, need_da, need_dw, dy16=None, db_pre=None):
+def _contract_bwd(kind, dy, a16, params, geo, need_da, need_dw, dy16=None, db_pre=None, *, sink=None):
     """dy fp32 contiguous -> (da fp32 | None, [parameter gradients in the order of `params`, bias included]).
     dy16 / db_pre: the gradient already rounded to the backward operand type and its column sums (the bias gradient),
-    when the caller produced them in one pass."""
+    when the caller produced them in one pass.  sink (planned engine): weight gradients go straight to its flat buffer."""
     dev = dy.device
     dt = _dt(GRAD_DTYPE)
     lib = _lib.load()
+    accumulate = sink is not None and bool(sink.accumulate)
 
     def bias_grad(bias, wanted):
         if bias is None or not wanted:
             return None
-        return db_pre if db_pre is not None else _colsum(dy)[0]
+        return db_pre if db_pre is not None else _colsum(dy, sink=sink)[0]
     if kind == "lin":
         weight, bias = params
-        dst = _sink_dest(weight) if need_dw[0] else None
+        dst = _sink_dest(sink, weight) if need_dw[0] else None
         da, dw = _grad_contractions(dy, a16, lambda d: PACK.get(weight, f"lin_t_{d}", _pack_lin_t(d)),
                                     need_da, need_dw[0], dy16,
-                                    dw_dest=None if dst is None else dst[0].reshape(weight.shape[0], -1))
+                                    dw_dest=None if dst is None else dst[0].reshape(weight.shape[0], -1),
+                                    accumulate=accumulate)
         if dw is not None:
             dw = dw.reshape(weight.shape)
         return da, [dw, bias_grad(bias, need_dw[1])]
     if kind == "qkv":
-        dst = _sink_dest(*params) if all(need_dw) else None
+        dst = _sink_dest(sink, *params) if all(need_dw) else None
         n = params[0].shape[0]
         da, dw = _grad_contractions(
             dy, a16,
             lambda d: PACK.get_multi(params, f"qkv_t_{d}",
                                      lambda ws: torch.cat([w.t().to(d) for w in ws], 1).contiguous()),
             need_da, any(need_dw), dy16,
-            dw_dest=None if dst is None else torch.as_strided(dst[0], (3 * n, params[0].shape[1]), (params[0].shape[1], 1)))
+            dw_dest=None if dst is None else torch.as_strided(dst[0], (3 * n, params[0].shape[1]), (params[0].shape[1], 1)),
+            accumulate=accumulate)
         if dw is None:
             return da, [None, None, None]
         return da, [dw[:n], dw[n:2 * n], dw[2 * n:]]
@@ -601,7 +594,7 @@ def _contract_bwd(kind, dy, a16, params, geo, need_da, need_dw, dy16=None, db_pr
         col = None
         # planned engine, stride-1 same-size convolutions: the weight gradient gathers its X operand per tap inside the
         # kernel (gcd_wgrad_conv_tr_f16) — no im2col tensor
-        dst = _sink_dest(weight) if need_dw[0] else None
+        dst = _sink_dest(sink, weight) if need_dw[0] else None
         implicit = dst is not None and geo["stride"] == 1 and not geo["upsample"] and WGRAD_IMPLICIT
         if (need_dw[0] and not implicit) or (need_da and da is None):
             xg = _as_dtype(a16, dt)
@@ -620,9 +613,9 @@ def _contract_bwd(kind, dy, a16, params, geo, need_da, need_dw, dy16=None, db_pr
             da = dxp[:, :Cin] if cin_p != Cin else dxp
         if need_dw[0]:
             if implicit:
-                dw = _wgrad_conv(dy16, _as_dtype(a16, dt), dst[0], 1, Cout, Cin, Ho=Ho, Wo=Wo)
+                dw = _wgrad_conv(dy16, _as_dtype(a16, dt), dst[0], 1, Cout, Cin, Ho=Ho, Wo=Wo, accumulate=accumulate)
             elif dst is not None:           # straight into the parameter's [Cout, Cin, 3, 3] slot, cropped
-                dw = _wgrad(dy16, col, dest=dst[0], taps=9, n_real=Cout, c_real=Cin)
+                dw = _wgrad(dy16, col, dest=dst[0], taps=9, n_real=Cout, c_real=Cin, accumulate=accumulate)
             else:
                 dwp = _wgrad(dy16, col)       # dW = dY^T col [cout_p, 9 * cin_p], contraction over the tokens
                 dw = dwp.reshape(cout_p, 3, 3, cin_p).permute(0, 3, 1, 2)[:Cout, :Cin].contiguous()
@@ -638,16 +631,16 @@ def _contract_bwd(kind, dy, a16, params, geo, need_da, need_dw, dy16=None, db_pr
             wd = PACK.get(weight, f"t3d_{dt}", _pack_t3_dgrad(dt))          # [Cin, 3*Cout]
             da = torch.empty(M, Cc, dtype=_f32, device=dev)
             _gemm(dy16, wd, da, M=M, mode=GEMM_TEMPORAL3, conv=dict(Cin=Cout, T=geo["T"], HW=geo["HW"]))
-        dst = _sink_dest(weight) if need_dw[0] else None
+        dst = _sink_dest(sink, weight) if need_dw[0] else None
         if need_dw[0] and dst is not None and WGRAD_IMPLICIT:
-            dw = _wgrad_conv(dy16, _as_dtype(a16, dt), dst[0], 2, Cout, Cc, T=geo["T"], HW=geo["HW"])
+            dw = _wgrad_conv(dy16, _as_dtype(a16, dt), dst[0], 2, Cout, Cc, T=geo["T"], HW=geo["HW"], accumulate=accumulate)
         elif need_dw[0]:
             xg = _as_dtype(a16, dt)
             col = torch.empty(M, 3 * Cc, dtype=dt, device=dev)
             check(lib.gcd_im2col_t3_f16(xg.data_ptr(), _ld(xg), col.data_ptr(), M, Cc, geo["T"], geo["HW"],
                                         _stream()), "gcd_im2col_t3_f16")
             if dst is not None:
-                dw = _wgrad(dy16, col, dest=dst[0], taps=3, n_real=Cout, c_real=Cc)
+                dw = _wgrad(dy16, col, dest=dst[0], taps=3, n_real=Cout, c_real=Cc, accumulate=accumulate)
             else:
                 dwp = _wgrad(dy16, col)
                 dw = dwp.reshape(Cout, 3, Cc).permute(0, 2, 1).reshape(Cout, Cc, 3, 1, 1).contiguous()
@@ -670,8 +663,9 @@ def _gn_fwd(x, gamma, beta, rows_per_inst, eps, silu, dtype=_f16):
     return y16, stats, g32, b32
 
 
-def _gn_bwd(x, dy, stats, g32, b32, rows_per_inst, silu, dest=None, dx_add=None):
-    """dest (planned engine): (dgamma, dbeta) slots of the flat gradient buffer, written by one small kernel."""
+def _gn_bwd(x, dy, stats, g32, b32, rows_per_inst, silu, dest=None, dx_add=None, *, accumulate: bool = False):
+    """dest (planned engine): (dgamma, dbeta) slots of the flat gradient buffer, written (accumulate: added to) by one small
+    kernel."""
     M, Cc = x.shape
     ninst = M // rows_per_inst
     lib = _lib.load()
@@ -687,8 +681,8 @@ def _gn_bwd(x, dy, stats, g32, b32, rows_per_inst, silu, dest=None, dx_add=None)
           "gcd_groupnorm_bwd")
     if dest is not None and dest[0] is not None and dest[1] is not None:
         _lib.check_train(_lib.load_train().gcd_gn_affine_grads(
-            AB.data_ptr(), ninst, Cc, dest[0].data_ptr(), dest[1].data_ptr(),
-            int(bool(_sink() is not None and _sink().accumulate)), _stream()), "gcd_gn_affine_grads")
+            AB.data_ptr(), ninst, Cc, dest[0].data_ptr(), dest[1].data_ptr(), int(accumulate), _stream()),
+            "gcd_gn_affine_grads")
         return dx, dest[0], dest[1]
     ab = AB.sum(0).float()
     return dx, ab[:, 1].contiguous(), ab[:, 0].contiguous()
@@ -711,140 +705,154 @@ def _ln_bwd(x, dy, g32, eps, dest=None, dx_add=None):
     else:
         dgb = torch.zeros(2, Cc, dtype=_f32, device=x.device)      # one fill for both accumulators
         dg, db = dgb[0], dgb[1]
-    if DETERMINISTIC:
-        _det_call("gcd_layernorm_bwd_det", int(_lib.load_train().gcd_layernorm_bwd_det_scratch_floats(M, Cc)), x.device,
-                  lambda lib, sp, sn: lib.gcd_layernorm_bwd_det(
-                      x.data_ptr(), _ld(x), dy.data_ptr(), _ld(dy), M, Cc, g32.data_ptr(), eps, dx.data_ptr(), _ld(dx),
-                      dg.data_ptr(), db.data_ptr(), 0 if dx_add is None else dx_add.data_ptr(),
-                      0 if dx_add is None else _ld(dx_add), sp, sn, _stream()))
-        return dx, dg, db
-    check(_lib.load().gcd_layernorm_bwd(x.data_ptr(), _ld(x), dy.data_ptr(), _ld(dy), M, Cc, g32.data_ptr(),
-                                        eps, dx.data_ptr(), _ld(dx), dg.data_ptr(), db.data_ptr(),
-                                        0 if dx_add is None else dx_add.data_ptr(), 0 if dx_add is None else _ld(dx_add),
-                                        _stream()), "gcd_layernorm_bwd")
+    _reduction((_lib.load, check, "gcd_layernorm_bwd"), "gcd_layernorm_bwd_det",
+               lambda lib: lib.gcd_layernorm_bwd_det_scratch_floats(M, Cc), x.device,
+               (x.data_ptr(), _ld(x), dy.data_ptr(), _ld(dy), M, Cc, g32.data_ptr(), eps, dx.data_ptr(), _ld(dx), dg.data_ptr(),
+                db.data_ptr(), 0 if dx_add is None else dx_add.data_ptr(), 0 if dx_add is None else _ld(dx_add)))
     return dx, dg, db
 
 
-class Fused(torch.autograd.Function):
-    """[norm ->] contraction [+ per-frame vector] [+ residual] as ONE graph node.
+# ---- the fused node without a tape: what both engines run.  `Fused` below is its adapter to torch.autograd, the planned
+# engine (train_plan.py) calls it directly ----
+# What fused_backward needs of a fused_forward: has = (residual, rowvec, bias given); tensors = [a16, the parameters that are
+# not None, then of the prologue geglu: x | ln: x, g32 | gn: x, g32, stats, b32] — the list `Fused` saves for backward.
+_FusedSaved = collections.namedtuple("_FusedSaved", "spec n_params has tensors")
 
-    apply(spec, x, residual, rowvec, gamma, beta, *params)
+
+def fused_forward(spec, x, residual, rowvec, gamma, beta, params, *, a16=None):
+    """[norm ->] contraction [+ per-frame vector] [+ residual] -> (y, _FusedSaved).
       spec: dict(kind = lin | qkv | c3 | t3, geo = {...}, norm = None | ("ln", eps) | ("gn", rows_per_inst,
-            eps, silu), rows_per_vec)
+            eps, silu) | ("geglu",), rows_per_vec)
+      a16: x as the 16-bit operand it already exists as (an attention core's fp16 output), for a node without a prologue.
     The normalised activation goes from the norm kernel to the GEMM as the 16-bit operand it is (no fp32
     round trip, no cast pass); bias, the per-frame vector (emb_layers output, openaimodel.py:343-347) and the
-    residual ride in the GEMM epilogue as in the inference engine.  Backward: the contraction's dgrad / wgrad,
-    the norm's backward, d residual = dy, d rowvec = per-frame row sums of dy."""
+    residual ride in the GEMM epilogue as in the inference engine."""
+    ops._need_gpu(x)
+    kind, geo, norm = spec["kind"], spec.get("geo"), spec.get("norm")
+    dt = _dt(FWD_DTYPE)
+    stats = g32 = b32 = None
+    if norm is not None and norm[0] == "geglu":
+        # x is the fp32 projection [value | gate] of a FeedForward (attention.py:87-97): value * gelu(gate),
+        # rounded once to the operand type, straight into the second Linear
+        x = x.contiguous()
+        M, H2 = x.shape
+        # (bf16 operands: rounded ONCE from fp32 — no fp16 hop, none of fp16's range on the hidden tensor)
+        a16 = torch.empty(M, H2 // 2, dtype=dt, device=x.device)
+        fn = _lib.load().gcd_geglu_fwd_bf16 if dt == _bf16 else _lib.load().gcd_geglu_fwd_f16
+        check(fn(x.data_ptr(), _ld(x), a16.data_ptr(), _ld(a16), M, H2 // 2, _stream()), "gcd_geglu_fwd_16")
+    elif norm is not None:
+        x = x.contiguous()
+        if norm[0] == "ln":
+            a16, g32 = _ln_fwd(x, gamma, beta, norm[1], dt)
+        else:
+            a16, stats, g32, b32 = _gn_fwd(x, gamma, beta, norm[1], norm[2], norm[3], dt)
+    elif a16 is not None:
+        a16 = _as_dtype(a16, dt)
+    elif kind == "c3" and _c3_dims(params[0], geo)[2] != x.shape[1]:
+        a16 = torch.zeros(x.shape[0], _c3_dims(params[0], geo)[2], dtype=dt, device=x.device)
+        _cast16_into(x, a16[:, :x.shape[1]])
+    else:
+        a16 = _cast16(x, dt)
+    bias = None if kind == "qkv" else params[1]
+    y = _contract_fwd(kind, a16, params, geo,
+                      _epi(bias, None if rowvec is None else (rowvec, spec["rows_per_vec"]), residual))
+    tensors = [a16] + [p for p in params if p is not None]
+    if norm is not None and norm[0] == "geglu":
+        tensors += [x]
+    elif norm is not None:
+        tensors += [x, g32] + ([stats, b32] if norm[0] == "gn" else [])
+    return y, _FusedSaved(spec, len(params), (residual is not None, rowvec is not None, bias is not None), tensors)
+
+
+def fused_backward(saved, dy, *, need_x, need_res, need_vec, need_norm, need_params, sink=None, bias_dest=None,
+                   norm_dest=None, dx_add=None):
+    """-> (dx, d_res, d_vec, dgamma, dbeta, [parameter gradients in the order of `params`]): the contraction's dgrad / wgrad,
+    the norm's backward, d residual = dy, d rowvec = per-frame row sums of dy; None for what is not needed (need_params: one
+    flag per parameter) or not there.  The planned engine's in-place destinations: sink (the plan: weight gradients,
+    accumulators from its arena), bias_dest / norm_dest = (dgamma, dbeta) (slots of its flat gradient buffer), and dx_add,
+    another gradient of x that the LayerNorm / GroupNorm backward kernel adds to dx."""
+    spec = saved.spec
+    kind, geo, norm = spec["kind"], spec.get("geo"), spec.get("norm")
+    has_res, has_vec, has_bias = saved.has
+    rest = list(saved.tensors)
+    a16 = rest.pop(0)
+    if kind == "qkv":
+        params = tuple(rest[:3])
+        rest = rest[3:]
+    else:
+        weight = rest.pop(0)
+        bias = rest.pop(0) if has_bias else None
+        params = (weight, bias)
+    dy = dy.contiguous()
+    need_da = need_x or (norm is not None and need_norm)
+    need_dw = list(need_params)
+    # ONE pass over dY: rounded to the backward operand type for the dgrad / wgrad GEMMs, and summed per row block
+    # for the bias gradient (one block) / the per-frame vector's gradient (one block per `rows_per_vec` rows)
+    want_db = has_bias and kind != "qkv" and need_dw[1]
+    want_vec = has_vec and need_vec
+    dy16 = db_pre = d_vec = None
+    if (want_db or want_vec) and _FUSE_DY_SUMS and dy.shape[1] % 8 == 0:
+        rows = spec["rows_per_vec"] if want_vec else dy.shape[0]
+        both = want_vec and want_db and bias_dest is not None
+        dy16, sums = _cast16_colsum(dy, _dt(GRAD_DTYPE), rows,
+                                    bias_dest.view(1, -1) if bias_dest is not None and want_db and not want_vec else None,
+                                    bias_dest if both else None, sink=sink)
+        if want_vec:
+            d_vec = sums
+        if want_db:
+            db_pre = bias_dest if both else (sums.sum(0) if want_vec else sums[0])
+    da, dps = _contract_bwd(kind, dy, a16, params, geo, need_da, need_dw, dy16, db_pre, sink=sink)
+    dgamma = dbeta = None
+    if norm is None:
+        dx = da
+    elif da is None:
+        dx = None
+    elif norm[0] == "geglu":
+        (h,) = rest
+        da = da.contiguous()
+        dx = torch.empty_like(h)
+        check(_lib.load().gcd_geglu_bwd_f32(h.data_ptr(), _ld(h), da.data_ptr(), _ld(da), dx.data_ptr(),
+                                            _ld(dx), h.shape[0], h.shape[1] // 2, _stream()), "gcd_geglu_bwd_f32")
+    elif norm[0] == "ln":
+        x, g32 = rest
+        dx, dgamma, dbeta = _ln_bwd(x, da.contiguous(), g32, norm[1], norm_dest, dx_add)
+    else:
+        x, g32, stats, b32 = rest
+        dx, dgamma, dbeta = _gn_bwd(x, da.contiguous(), stats, g32, b32, norm[1], norm[3], norm_dest, dx_add,
+                                    accumulate=sink is not None and bool(sink.accumulate))
+    d_res = dy if has_res and need_res else None
+    if want_vec and d_vec is None:
+        d_vec = _colsum(dy, spec["rows_per_vec"], sink=sink)
+    return dx if need_x else None, d_res, d_vec, dgamma, dbeta, dps
+
+
+class Fused(torch.autograd.Function):
+    """fused_forward / fused_backward as ONE graph node: apply(spec, x, residual, rowvec, gamma, beta, *params)."""
 
     @staticmethod
     def forward(ctx, spec, x, residual, rowvec, gamma, beta, *params):
-        ops._need_gpu(x)
-        kind, geo, norm = spec["kind"], spec.get("geo"), spec.get("norm")
-        dt = _dt(FWD_DTYPE)
-        stats = g32 = b32 = None
-        if norm is not None and norm[0] == "geglu":
-            # x is the fp32 projection [value | gate] of a FeedForward (attention.py:87-97): value * gelu(gate),
-            # rounded once to the operand type, straight into the second Linear
-            x = x.contiguous()
-            M, H2 = x.shape
-            # (bf16 operands: rounded ONCE from fp32 — no fp16 hop, none of fp16's range on the hidden tensor)
-            a16 = torch.empty(M, H2 // 2, dtype=dt, device=x.device)
-            fn = _lib.load().gcd_geglu_fwd_bf16 if dt == _bf16 else _lib.load().gcd_geglu_fwd_f16
-            check(fn(x.data_ptr(), _ld(x), a16.data_ptr(), _ld(a16), M, H2 // 2, _stream()), "gcd_geglu_fwd_16")
-        elif norm is not None:
-            x = x.contiguous()
-            if norm[0] == "ln":
-                a16, g32 = _ln_fwd(x, gamma, beta, norm[1], dt)
-            else:
-                a16, stats, g32, b32 = _gn_fwd(x, gamma, beta, norm[1], norm[2], norm[3], dt)
-        elif _f16_passthrough_on() and getattr(x, "_gcd_f16", None) is not None and x._gcd_f16[1] == x._version and \
+        a16 = None
+        if spec.get("norm") is None and _f16_passthrough_on() and getattr(x, "_gcd_f16", None) is not None and x._gcd_f16[1] == x._version and \
                 x._gcd_f16[0].shape == x.shape:
             # x is the fp32 image of an fp16 tensor an attention core produced: that tensor IS the operand
-            a16 = _as_dtype(x._gcd_f16[0], dt)
-        elif kind == "c3" and _c3_dims(params[0], geo)[2] != x.shape[1]:
-            a16 = torch.zeros(x.shape[0], _c3_dims(params[0], geo)[2], dtype=dt, device=x.device)
-            _cast16_into(x, a16[:, :x.shape[1]])
-        else:
-            a16 = _cast16(x, dt)
-        bias = None if kind == "qkv" else params[1]
-        y = _contract_fwd(kind, a16, params, geo,
-                          _epi(bias, None if rowvec is None else (rowvec, spec["rows_per_vec"]), residual))
-        ctx.spec = spec
-        ctx.n_params = len(params)
-        ctx.has = (residual is not None, rowvec is not None, bias is not None)
-        tensors = [a16] + [p for p in params if p is not None]
-        if norm is not None and norm[0] == "geglu":
-            tensors += [x]
-        elif norm is not None:
-            tensors += [x, g32] + ([stats, b32] if norm[0] == "gn" else [])
-        ctx.save_for_backward(*tensors)
+            a16 = x._gcd_f16[0]
+        y, saved = fused_forward(spec, x, residual, rowvec, gamma, beta, params, a16=a16)
+        ctx.spec, ctx.n_params, ctx.has = saved.spec, saved.n_params, saved.has
+        ctx.save_for_backward(*saved.tensors)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        spec = ctx.spec
-        kind, geo, norm = spec["kind"], spec.get("geo"), spec.get("norm")
-        has_res, has_vec, has_bias = ctx.has
-        saved = list(ctx.saved_tensors)
-        a16 = saved.pop(0)
-        if kind == "qkv":
-            params = tuple(saved[:3])
-            saved = saved[3:]
-        else:
-            weight = saved.pop(0)
-            bias = saved.pop(0) if has_bias else None
-            params = (weight, bias)
-        dy = dy.contiguous()
         nig = ctx.needs_input_grad          # (spec, x, residual, rowvec, gamma, beta, *params)
-        need_x = nig[1]
-        need_norm_params = norm is not None and (nig[4] or nig[5])
-        need_da = need_x or need_norm_params
-        need_dw = list(nig[6:6 + ctx.n_params])
-        # ONE pass over dY: rounded to the backward operand type for the dgrad / wgrad GEMMs, and summed per row block
-        # for the bias gradient (one block) / the per-frame vector's gradient (one block per `rows_per_vec` rows)
-        want_db = has_bias and kind != "qkv" and need_dw[1]
-        want_vec = has_vec and nig[3]
-        dy16 = db_pre = d_vec = None
-        bias_dest = getattr(ctx, "bias_dest", None)        # planned engine: slots of the flat gradient buffer
-        norm_dest = getattr(ctx, "norm_dest", None)
-        if (want_db or want_vec) and _FUSE_DY_SUMS and dy.shape[1] % 8 == 0:
-            rows = spec["rows_per_vec"] if want_vec else dy.shape[0]
-            both = want_vec and want_db and bias_dest is not None
-            dy16, sums = _cast16_colsum(dy, _dt(GRAD_DTYPE), rows,
-                                        bias_dest.view(1, -1) if bias_dest is not None and want_db and not want_vec else None,
-                                        bias_dest if both else None)
-            if want_vec:
-                d_vec = sums
-            if want_db:
-                db_pre = bias_dest if both else (sums.sum(0) if want_vec else sums[0])
-        da, dps = _contract_bwd(kind, dy, a16, params, geo, need_da, need_dw, dy16, db_pre)
-        dgamma = dbeta = None
-        if norm is None:
-            dx = da
-        elif da is None:
-            dx = None
-        elif norm[0] == "geglu":
-            (h,) = saved
-            da = da.contiguous()
-            dx = torch.empty_like(h)
-            check(_lib.load().gcd_geglu_bwd_f32(h.data_ptr(), _ld(h), da.data_ptr(), _ld(da), dx.data_ptr(),
-                                                _ld(dx), h.shape[0], h.shape[1] // 2, _stream()), "gcd_geglu_bwd_f32")
-        elif norm[0] == "ln":
-            x, g32 = saved
-            dx, dgamma, dbeta = _ln_bwd(x, da.contiguous(), g32, norm[1], norm_dest, getattr(ctx, "dx_add", None))
-        else:
-            x, g32, stats, b32 = saved
-            dx, dgamma, dbeta = _gn_bwd(x, da.contiguous(), stats, g32, b32, norm[1], norm[3], norm_dest,
-                                        getattr(ctx, "dx_add", None))
-        d_res = dy if has_res and nig[2] else None
-        if want_vec and d_vec is None:
-            d_vec = _colsum(dy, spec["rows_per_vec"])
-        return (None, dx if need_x else None, d_res, d_vec, dgamma, dbeta, *dps)
+        dx, d_res, d_vec, dgamma, dbeta, dps = fused_backward(
+            _FusedSaved(ctx.spec, ctx.n_params, ctx.has, ctx.saved_tensors), dy, need_x=nig[1], need_res=nig[2],
+            need_vec=nig[3], need_norm=nig[4] or nig[5], need_params=nig[6:6 + ctx.n_params])
+        return (None, dx, d_res, d_vec, dgamma, dbeta, *dps)
 
 
-def _fused(kind, x, params, geo=None, norm=None, residual=None, rowvec=None):
-    """norm: None | ("ln", module, eps) | ("gn", module, rows_per_inst, eps, silu) | ("geglu",): the prologue applied
-    to x; rowvec: (vector [n, N], rows)."""
+def _spec(kind, geo=None, norm=None, rowvec=None):
+    """-> (spec, gamma, beta) of a fused node.  norm: None | ("ln", module, eps) | ("gn", module, rows_per_inst, eps, silu) |
+    ("geglu",): the prologue applied to x; rowvec: (vector [n, N], rows)."""
     spec = dict(kind=kind, geo=geo, norm=None, rows_per_vec=None if rowvec is None else rowvec[1])
     gamma = beta = None
     if norm is not None and norm[0] == "geglu":
@@ -852,6 +860,11 @@ def _fused(kind, x, params, geo=None, norm=None, residual=None, rowvec=None):
     elif norm is not None:
         gamma, beta = norm[1].weight, norm[1].bias
         spec["norm"] = (norm[0],) + tuple(norm[2:])
+    return spec, gamma, beta
+
+
+def _fused(kind, x, params, geo=None, norm=None, residual=None, rowvec=None):
+    spec, gamma, beta = _spec(kind, geo, norm, rowvec)
     return Fused.apply(spec, x, residual, None if rowvec is None else rowvec[0], gamma, beta, *params)
 
 
@@ -865,14 +878,18 @@ def qkv_linear(x, wq, wk, wv, *, norm=None):
     return _fused("qkv", x, (wq, wk, wv), norm=norm)
 
 
-def conv3x3(x, weight, bias, frames, Hi, Wi, stride=1, upsample=False, *, norm=None, residual=None, rowvec=None):
+def _c3_geo(frames, Hi, Wi, stride=1, upsample=False):
     if upsample:
         Ho, Wo = 2 * Hi, 2 * Wi
     else:
         Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
+    return dict(frames=frames, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo, stride=stride, upsample=int(upsample))
+
+
+def conv3x3(x, weight, bias, frames, Hi, Wi, stride=1, upsample=False, *, norm=None, residual=None, rowvec=None):
     assert x.shape[0] == frames * Hi * Wi and x.shape[1] == weight.shape[1]
-    geo = dict(frames=frames, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo, stride=stride, upsample=int(upsample))
-    return _fused("c3", x, (weight, bias), geo=geo, norm=norm, residual=residual, rowvec=rowvec)
+    return _fused("c3", x, (weight, bias), geo=_c3_geo(frames, Hi, Wi, stride, upsample), norm=norm, residual=residual,
+                  rowvec=rowvec)
 
 
 def conv_t3(x, weight, bias, T, HW, *, norm=None, residual=None, rowvec=None):
@@ -959,37 +976,44 @@ def geglu(h):
 # forward: the flash kernel of the inference path; backward: the flash-style kernels of attn_bwd.hip
 # (dV = P^T dO, dP = dO V^T, dS = P (dP - rowsum(dO O)) / 8, dQ = dS K, dK = dS^T Q, P recomputed per tile).
 # ------------------------------------------------------------------------------------------------
+def spatial_attention_forward(qkv, frames, S, heads):
+    """-> (out16 [M, C] fp16, saved)"""
+    ops._need_gpu(qkv)
+    M, C3 = qkv.shape
+    Cc = C3 // 3
+    assert M == frames * S and Cc == heads * 64
+    qkv16 = qkv if qkv.dtype == _f16 and qkv.is_contiguous() else _cast16(qkv.contiguous())
+    S_pad = (S + 63) // 64 * 64
+    vt = torch.empty(frames * heads * 64 * S_pad, dtype=_f16, device=qkv.device)
+    ops.attn_transpose_v(qkv16, frames, S, heads, vt, S_pad)
+    out16 = torch.empty(M, Cc, dtype=_f16, device=qkv.device)
+    ops.attn_spatial(qkv16, vt, S_pad, out16, frames, S, heads, q_prescaled=False)
+    return out16, (qkv16, out16, (frames, S, heads))
+
+
+def spatial_attention_backward(saved, dO):
+    """-> dqkv fp32.  Flash-style backward on gcd_attn_spatial_bwd (attn_bwd.hip): P is recomputed tile by tile from a
+    per-query log-sum-exp, one launch sequence for all (frame, head) pairs."""
+    qkv16, out16, (frames, S, heads) = saved
+    dO16 = _cast16(dO.contiguous())
+    dqkv = torch.empty(frames * S, 3 * heads * 64, dtype=_f32, device=dO.device)
+    ws = _attn_ws(dO.device, ops.attn_spatial_bwd_ws_bytes(frames, S, heads))
+    ops.attn_spatial_bwd(qkv16, out16, dO16, dqkv, frames, S, heads, ws)
+    return dqkv
+
+
 class SpatialAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, frames, S, heads):
-        ops._need_gpu(qkv)
-        M, C3 = qkv.shape
-        Cc = C3 // 3
-        assert M == frames * S and Cc == heads * 64
-        qkv16 = qkv if qkv.dtype == _f16 and qkv.is_contiguous() else _cast16(qkv.contiguous())
-        S_pad = (S + 63) // 64 * 64
-        vt = torch.empty(frames * heads * 64 * S_pad, dtype=_f16, device=qkv.device)
-        ops.attn_transpose_v(qkv16, frames, S, heads, vt, S_pad)
-        out16 = torch.empty(M, Cc, dtype=_f16, device=qkv.device)
-        ops.attn_spatial(qkv16, vt, S_pad, out16, frames, S, heads, q_prescaled=False)
-        ctx.save_for_backward(qkv16, out16)
-        ctx.dims = (frames, S, heads)
-        if getattr(ctx, "want16", False):      # planned engine: the fp16 result IS the next Linear's operand (no fp32 image)
-            return out16
+        out16, saved = spatial_attention_forward(qkv, frames, S, heads)
+        ctx.save_for_backward(*saved[:2])
+        ctx.dims = saved[2]
         _LAST_F16[0] = out16
         return out16.float()
 
     @staticmethod
     def backward(ctx, dO):
-        """Flash-style backward on gcd_attn_spatial_bwd (attn_bwd.hip): P is recomputed tile by tile from a
-        per-query log-sum-exp, one launch sequence for all (frame, head) pairs."""
-        qkv16, out16 = ctx.saved_tensors
-        frames, S, heads = ctx.dims
-        dO16 = _cast16(dO.contiguous())
-        dqkv = torch.empty(frames * S, 3 * heads * 64, dtype=_f32, device=dO.device)
-        ws = _attn_ws(dO.device, ops.attn_spatial_bwd_ws_bytes(frames, S, heads))
-        ops.attn_spatial_bwd(qkv16, out16, dO16, dqkv, frames, S, heads, ws)
-        return dqkv, None, None, None
+        return spatial_attention_backward((*ctx.saved_tensors, ctx.dims), dO), None, None, None
 
 
 _LAST_F16 = [None]
@@ -1029,36 +1053,42 @@ def spatial_attention(qkv, frames, S, heads):
     return _with_f16(SpatialAttention.apply(qkv, frames, S, heads))
 
 
-class TemporalAttention(torch.autograd.Function):
+def temporal_attention_forward(qkv, clips, T, HW, heads):
     """Self-attention over the T frames of every pixel (video_attention.py:114-139 after the
-    (b t) s c -> (b s) t c rearrange): rows stay (clip, t, hw)."""
+    (b t) s c -> (b s) t c rearrange): rows stay (clip, t, hw).  -> (out16 [M, C] fp16, saved)"""
+    ops._need_gpu(qkv)
+    M, C3 = qkv.shape
+    Cc = C3 // 3
+    qkv16 = qkv if qkv.dtype == _f16 and qkv.is_contiguous() else _cast16(qkv.contiguous())
+    out16 = torch.empty(M, Cc, dtype=_f16, device=qkv.device)
+    ops.attn_temporal(qkv16, out16, clips, T, HW, heads)
+    return out16, (qkv16, (clips, T, HW, heads))
 
+
+def temporal_attention_backward(saved, dO):
+    """-> dqkv fp32"""
+    qkv16, (clips, T, HW, heads) = saved
+    dO = dO.contiguous()
+    dqkv = torch.empty(qkv16.shape, dtype=_f32, device=dO.device)
+    # T <= 16: gcd_attn_temporal_bwd; 17..64: gcd_attn_temporal_long_bwd (which refuses T > 64)
+    name = "gcd_attn_temporal_bwd" if T <= 16 else "gcd_attn_temporal_long_bwd"
+    check(getattr(_lib.load(), name)(qkv16.data_ptr(), _ld(qkv16), dO.data_ptr(), _ld(dO), dqkv.data_ptr(),
+                                     _ld(dqkv), clips, T, HW, heads, _stream()), name)
+    return dqkv
+
+
+class TemporalAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, clips, T, HW, heads):
-        ops._need_gpu(qkv)
-        M, C3 = qkv.shape
-        Cc = C3 // 3
-        qkv16 = qkv if qkv.dtype == _f16 and qkv.is_contiguous() else _cast16(qkv.contiguous())
-        out16 = torch.empty(M, Cc, dtype=_f16, device=qkv.device)
-        ops.attn_temporal(qkv16, out16, clips, T, HW, heads)
-        ctx.save_for_backward(qkv16)
-        ctx.dims = (clips, T, HW, heads)
-        if getattr(ctx, "want16", False):
-            return out16
+        out16, saved = temporal_attention_forward(qkv, clips, T, HW, heads)
+        ctx.save_for_backward(saved[0])
+        ctx.dims = saved[1]
         _LAST_F16[0] = out16
         return out16.float()
 
     @staticmethod
     def backward(ctx, dO):
-        (qkv16,) = ctx.saved_tensors
-        clips, T, HW, heads = ctx.dims
-        dO = dO.contiguous()
-        dqkv = torch.empty(qkv16.shape, dtype=_f32, device=dO.device)
-        # T <= 16: gcd_attn_temporal_bwd; 17..64: gcd_attn_temporal_long_bwd (which refuses T > 64)
-        name = "gcd_attn_temporal_bwd" if T <= 16 else "gcd_attn_temporal_long_bwd"
-        check(getattr(_lib.load(), name)(qkv16.data_ptr(), _ld(qkv16), dO.data_ptr(), _ld(dO), dqkv.data_ptr(),
-                                         _ld(dqkv), clips, T, HW, heads, _stream()), name)
-        return dqkv, None, None, None, None
+        return temporal_attention_backward((*ctx.saved_tensors, ctx.dims), dO), None, None, None, None
 
 
 def temporal_attention(qkv, clips, T, HW, heads):

@@ -65,84 +65,47 @@ def _notify(plan, p) -> None:
             fn(p)
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-class _Ctx:
-    """What `autograd_ops.Fused.forward / backward` (and the attention Functions) need of a torch ctx — their static methods
-    are called directly, there is no tape."""
-    needs_input_grad = ()
-
-    def save_for_backward(self, *t):
-        self.saved_tensors = t
-
-
 # ------------------------------------------------------------------------------------------------------------------------
-# operator wrappers: forward returns (y, ctx); backward takes (ctx, dy)
+# operator wrappers: forward returns (y, ctx) with ctx = (what autograd_ops.fused_forward saved, params, norm module | None);
+# backward takes (ctx, dy)
 # ------------------------------------------------------------------------------------------------------------------------
-def _fused_fwd(kind, x, params, geo=None, norm=None, residual=None, rowvec=None):
+def _fused_fwd(kind, x, params, geo=None, norm=None, residual=None, rowvec=None, a16=None):
     """norm: None | ("ln", module, eps) | ("gn", module, rows_per_inst, eps, silu) | ("geglu",); rowvec: (vec, rows)."""
-    spec = dict(kind=kind, geo=geo, norm=None, rows_per_vec=None if rowvec is None else rowvec[1])
-    gamma = beta = None
-    if norm is not None and norm[0] == "geglu":
-        spec["norm"] = ("geglu",)
-    elif norm is not None:
-        gamma, beta = norm[1].weight, norm[1].bias
-        spec["norm"] = (norm[0],) + tuple(norm[2:])
-    ctx = _Ctx()
-    ctx.params = params
-    ctx.norm_mod = None if gamma is None else norm[1]
-    y = A.Fused.forward(ctx, spec, x, residual, None if rowvec is None else rowvec[0], gamma, beta, *params)
-    return y, ctx
+    spec, gamma, beta = A._spec(kind, geo, norm, rowvec)
+    y, saved = A.fused_forward(spec, x, residual, None if rowvec is None else rowvec[0], gamma, beta, params, a16=a16)
+    return y, (saved, params, None if gamma is None else norm[1])
 
 
 def _fused_fwd_from16(kind, x16, params, residual=None, rowvec=None):
     """A Linear whose input already exists as the 16-bit operand (an attention core's fp16 output): no fp32 image of it, no
-    cast back (autograd_ops' fp16 pass-through, which the autograd engine measured slower because it holds the tensors)."""
-    x16._gcd_f16 = (x16, x16._version)
-    try:
-        with A.f16_passthrough(True):
-            return _fused_fwd(kind, x16, params, residual=residual, rowvec=rowvec)
-    finally:
-        del x16._gcd_f16          # (the tag refers to the tensor itself: no reference cycle left behind)
+    cast back (what the autograd engine's fp16 pass-through does, measured slower there because it holds the tensors)."""
+    return _fused_fwd(kind, x16, params, residual=residual, rowvec=rowvec, a16=x16)
 
 
-def _fused_bwd(plan: "TrainPlan", ctx: _Ctx, dy: torch.Tensor, need_x: bool = True, need_vec: bool = True, dx_add=None):
-    """-> (dx | None, d_vec | None).  Parameter gradients go to `plan.sink`.  dx_add: another gradient of the same input
-    (the residual branch's), added to dx — inside the LayerNorm / GroupNorm backward kernel when the node has one."""
-    has_res, has_vec, has_bias = ctx.has
-    norm = ctx.spec.get("norm")
+def _fused_bwd(plan: "TrainPlan", ctx, dy: torch.Tensor, need_x: bool = True, need_vec: bool = True, dx_add=None):
+    """-> (dx | None, d_vec | None).  Parameter gradients go to `plan.sink`, weight gradients written in place
+    (autograd_ops._sink_dest).  dx_add: another gradient of the same input (the residual branch's), added to dx — inside
+    the LayerNorm / GroupNorm backward kernel when the node has one."""
+    saved, params, gm = ctx
+    norm = saved.spec.get("norm")
     fused_add = dx_add is not None and norm is not None and norm[0] in ("ln", "gn")
-    ctx.dx_add = dx_add.contiguous() if fused_add else None
-    params = ctx.params
-    want = [p is not None and p.requires_grad for p in params]
-    gm = ctx.norm_mod
     want_norm = gm is not None and gm.weight.requires_grad
-    ctx.needs_input_grad = (False, need_x, has_res, has_vec and need_vec, want_norm, want_norm, *want)
-    ctx.norm_dest = (plan.grad_dest(gm.weight), plan.grad_dest(gm.bias)) if want_norm else None
     bias = params[1] if len(params) == 2 else None
-    ctx.bias_dest = plan.grad_dest(bias) if bias is not None and bias.requires_grad else None
-    with A.grad_sink(plan):                # weight gradients are written in place (autograd_ops._sink_dest)
-        out = A.Fused.backward(ctx, dy)
-    dx, d_vec, dgamma, dbeta = out[1], out[3], out[4], out[5]
+    dx, _, d_vec, dgamma, dbeta, dps = A.fused_backward(
+        saved, dy, need_x=need_x, need_res=False, need_vec=need_vec, need_norm=want_norm,
+        need_params=[p is not None and p.requires_grad for p in params], sink=plan,
+        bias_dest=plan.grad_dest(bias) if bias is not None and bias.requires_grad else None,
+        norm_dest=(plan.grad_dest(gm.weight), plan.grad_dest(gm.bias)) if want_norm else None,
+        dx_add=dx_add.contiguous() if fused_add else None)
     if dx_add is not None and not fused_add and dx is not None:
         dx = dx.add_(dx_add)
     if want_norm:
         plan.sink(gm.weight, dgamma)
         plan.sink(gm.bias, dbeta)
-    for p, g in zip(params, out[6:]):
+    for p, g in zip(params, dps):
         if p is not None and g is not None:
             plan.sink(p, g)
     return dx, d_vec
-
-
-def _c3_geo(frames, Hi, Wi, stride=1, upsample=False):
-    if upsample:
-        Ho, Wo = 2 * Hi, 2 * Wi
-    else:
-        Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
-    return dict(frames=frames, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo, stride=stride, upsample=int(upsample))
 
 
 def _ln(m):
@@ -271,7 +234,7 @@ class _SmallGroup:
     def forward(self, plan):
         dev, n, blocks = self._table("fwd", plan)
         if n:
-            _lib.check_train(_lib.load_train().gcd_smallm_fwd(dev.data_ptr(), n, blocks, _stream()), "gcd_smallm_fwd")
+            _lib.check_train(_lib.load_train().gcd_smallm_fwd(dev.data_ptr(), n, blocks, A._stream()), "gcd_smallm_fwd")
 
     def backward(self, plan, dys: List[torch.Tensor]):
         """dys[i]: gradient of item i's output (fp32 [M, N]); parameter gradients go to the flat buffer, input gradients
@@ -281,16 +244,13 @@ class _SmallGroup:
             it["dy"] = dy
         self._tabs.pop("dgrad", None)
         self._tabs.pop("wgrad", None)
-        lib = _lib.load_train()
         dev, n, blocks = self._table("dgrad", plan)
-        if n and A.DETERMINISTIC:
-            A._det_call("gcd_smallm_dgrad_det", int(lib.gcd_smallm_dgrad_det_scratch_floats(blocks)), self.device,
-                        lambda lib_, sp, sn: lib_.gcd_smallm_dgrad_det(dev.data_ptr(), n, blocks, sp, sn, _stream()))
-        elif n:
-            _lib.check_train(lib.gcd_smallm_dgrad(dev.data_ptr(), n, blocks, _stream()), "gcd_smallm_dgrad")
+        if n:
+            A._reduction((_lib.load_train, _lib.check_train, "gcd_smallm_dgrad"), "gcd_smallm_dgrad_det",
+                         lambda lib: lib.gcd_smallm_dgrad_det_scratch_floats(blocks), self.device, (dev.data_ptr(), n, blocks))
         dev, n, blocks = self._table("wgrad", plan)
         if n:
-            _lib.check_train(lib.gcd_smallm_wgrad(dev.data_ptr(), n, blocks, _stream()), "gcd_smallm_wgrad")
+            _lib.check_train(_lib.load_train().gcd_smallm_wgrad(dev.data_ptr(), n, blocks, A._stream()), "gcd_smallm_wgrad")
         for it in self.items:
             for p in (it["w"], it["b"]):
                 if p is not None and p.requires_grad:
@@ -312,7 +272,7 @@ class _ResUnit:
         N, T = plan.N, plan.T
         HW = H * W
         e2d, et = plan.emb_vecs[self.idx]
-        geo = _c3_geo(N, H, W)
+        geo = A._c3_geo(N, H, W)
         h, c1 = _fused_fwd("c3", x, (rb.in_layers[2].weight, rb.in_layers[2].bias), geo=geo,
                            norm=("gn", rb.in_layers[0], HW, 1e-5, True), rowvec=(e2d, HW))
         cs = None
@@ -397,9 +357,7 @@ class _AttnUnit:
             # spatial BasicTransformerBlock (attention.py:551-572)
             qkv, cq = _fused_fwd("qkv", h, (sb.attn1.to_q.weight, sb.attn1.to_k.weight, sb.attn1.to_v.weight), norm=_ln(sb.norm1),
                                  geo=_QKV16)
-            sa = _Ctx()
-            sa.want16 = True
-            o = A.SpatialAttention.forward(sa, qkv, N, HW, heads)
+            o, sa = A.spatial_attention_forward(qkv, N, HW, heads)
             del qkv
             h1, co = _fused_fwd_from16("lin", o, (sb.attn1.to_out[0].weight, sb.attn1.to_out[0].bias), residual=h,
                                        rowvec=(ca_s, HW))
@@ -412,9 +370,7 @@ class _AttnUnit:
             xm = self._ff(tb.ff_in, xm, tb.norm_in, cl)
             qkv, cq = _fused_fwd("qkv", xm, (tb.attn1.to_q.weight, tb.attn1.to_k.weight, tb.attn1.to_v.weight), norm=_ln(tb.norm1),
                                  geo=_QKV16)
-            ta = _Ctx()
-            ta.want16 = True
-            o = A.TemporalAttention.forward(ta, qkv, clips, T, HW, heads)
+            o, ta = A.temporal_attention_forward(qkv, clips, T, HW, heads)
             del qkv
             xm2, co = _fused_fwd_from16("lin", o, (tb.attn1.to_out[0].weight, tb.attn1.to_out[0].bias), residual=xm,
                                         rowvec=(ca_t, T * HW))
@@ -444,7 +400,7 @@ class _AttnUnit:
             del d_xm3
             # xm2 = to_out(attn(qkv(ln(xm1)))) + ca_t + xm1
             do, d_ca_t = _fused_bwd(plan, co2, d_xm2)
-            dqkv = A.TemporalAttention.backward(ta, do)[0]
+            dqkv = A.temporal_attention_backward(ta, do)
             del do
             d_xm1, _ = _fused_bwd(plan, cq2, dqkv, dx_add=d_xm2)
             del dqkv, d_xm2
@@ -456,7 +412,7 @@ class _AttnUnit:
             d_h1 = self._ff_bwd(cf1a, cf1b, d_h2)
             del d_h2
             do, d_ca_s = _fused_bwd(plan, co1, d_h1)
-            dqkv = A.SpatialAttention.backward(sa, do)[0]
+            dqkv = A.spatial_attention_backward(sa, do)
             del do
             dh, _ = _fused_bwd(plan, cq1, dqkv, dx_add=d_h1)
             del dqkv, d_h1
@@ -474,12 +430,12 @@ class _ConvUnit:
         self.plan, self.conv, self.stride, self.upsample, self.norm, self.first = plan, conv, stride, upsample, norm, first
 
     def out_hw(self, H, W):
-        g = _c3_geo(1, H, W, self.stride, self.upsample)
+        g = A._c3_geo(1, H, W, self.stride, self.upsample)
         return g["Ho"], g["Wo"]
 
     def fwd(self, x, H, W, save: bool):
         norm = None if self.norm is None else ("gn", self.norm, H * W, 1e-5, True)
-        y, c = _fused_fwd("c3", x, (self.conv.weight, self.conv.bias), geo=_c3_geo(self.plan.N, H, W, self.stride, self.upsample),
+        y, c = _fused_fwd("c3", x, (self.conv.weight, self.conv.bias), geo=A._c3_geo(self.plan.N, H, W, self.stride, self.upsample),
                           norm=norm)
         return y, (c if save else None)
 
@@ -702,7 +658,7 @@ class TrainPlan:
             self._build_pack_tables(fdt, gdt)
         lib = _lib.load_train()
         for dev_tab, n, tiles, bf16 in self._pack_tables:
-            _lib.check_train(lib.gcd_train_pack_weights(dev_tab.data_ptr(), n, tiles, bf16, _stream()),
+            _lib.check_train(lib.gcd_train_pack_weights(dev_tab.data_ptr(), n, tiles, bf16, A._stream()),
                              "gcd_train_pack_weights")
         A.PACK.clear()
         for owners, kind, tensor in self._pack_forms:
@@ -859,7 +815,7 @@ class TrainPlan:
         y = torch.empty_like(xs)
         _lib.check_train(_lib.load_train().gcd_blend_fwd_f32(xs.data_ptr(), xs.stride(0), xt.data_ptr(), xt.stride(0),
                                                              a.data_ptr(), xs.shape[0], xs.shape[1], rows, y.data_ptr(),
-                                                             y.stride(0), _stream()), "gcd_blend_fwd_f32")
+                                                             y.stride(0), A._stream()), "gcd_blend_fwd_f32")
         return y
 
     def blend_bwd(self, blender, dy, xs, xt, rows, want_xs: bool = True):
@@ -869,19 +825,12 @@ class TrainPlan:
         d_xs, d_xt = (torch.empty_like(dy) if want_xs else None), torch.empty_like(dy)
         want = blender.merge_strategy != "fixed" and blender.mix_factor.requires_grad
         dal = self._dalpha[slot] if want else None
-        if A.DETERMINISTIC:
-            M_, C_ = dy.shape
-            A._det_call("gcd_blend_bwd_det_f32", int(_lib.load_train().gcd_blend_bwd_det_scratch_floats(M_, C_, rows)),
-                        self.device, lambda lib, sp, sn: lib.gcd_blend_bwd_det_f32(
-                            dy.data_ptr(), dy.stride(0), xs.data_ptr(), xs.stride(0), xt.data_ptr(), xt.stride(0),
-                            a.data_ptr(), M_, C_, rows, 0 if d_xs is None else d_xs.data_ptr(), dy.stride(0), 0,
-                            d_xt.data_ptr(), d_xt.stride(0), 0 if dal is None else dal.data_ptr(), sp, sn, _stream()))
-            return d_xs, d_xt
-        _lib.check_train(_lib.load_train().gcd_blend_bwd_f32(
-            dy.data_ptr(), dy.stride(0), xs.data_ptr(), xs.stride(0), xt.data_ptr(), xt.stride(0), a.data_ptr(),
-            dy.shape[0], dy.shape[1], rows, 0 if d_xs is None else d_xs.data_ptr(), dy.stride(0), 0, d_xt.data_ptr(),
-            d_xt.stride(0),
-            0 if dal is None else dal.data_ptr(), _stream()), "gcd_blend_bwd_f32")
+        M, Cc = dy.shape
+        A._reduction((_lib.load_train, _lib.check_train, "gcd_blend_bwd_f32"), "gcd_blend_bwd_det_f32",
+                     lambda lib: lib.gcd_blend_bwd_det_scratch_floats(M, Cc, rows), self.device,
+                     (dy.data_ptr(), dy.stride(0), xs.data_ptr(), xs.stride(0), xt.data_ptr(), xt.stride(0), a.data_ptr(), M, Cc,
+                      rows, 0 if d_xs is None else d_xs.data_ptr(), dy.stride(0), 0, d_xt.data_ptr(), d_xt.stride(0),
+                      0 if dal is None else dal.data_ptr()))
         return d_xs, d_xt
 
     def add_rowvec(self, x, vec, rows):
@@ -889,8 +838,7 @@ class TrainPlan:
         return x + vec.repeat_interleave(rows, dim=0)
 
     def rowblock_sum(self, x, rows):
-        with A.grad_sink(self):
-            return A._colsum(x.contiguous(), rows)
+        return A._colsum(x.contiguous(), rows, sink=self)
 
     # ---- forward ----
     def forward(self, x, timesteps, context, y, num_video_frames: int, image_only_indicator, record: bool = True):

@@ -852,3 +852,124 @@ def test_bf16_gradient_contractions(gpu):
         assert worst < 1.5e-2
     finally:
         A.set_grad_dtype("fp16")
+
+
+# ------------------------------------------------------------ the tape-free operator core vs its autograd adapters
+def _core_form(form, gpu):
+    """-> (kind, x, params, geo, norm, residual, rowvec, dy) on the GPU, at the shapes of
+    test_fused_node_norm_contraction_vector_residual: 4 frames of 8 x 8 tokens (M = 256, more than one row block),
+    C = 64 -> 128 (K % 32, N % 16, 32 GroupNorm groups), one vector per 64 rows, T = 2 for the (3,1,1) convolution."""
+    g = _gen(47)
+    frames, H, W, C, Co, T = 4, 8, 8, 64, 128, 2
+    HW, M = H * W, 4 * 64
+
+    def rnd(*shape, scale=1.0):
+        return (torch.randn(*shape, generator=g) * scale).to(gpu)
+
+    def affine(mod):
+        with torch.no_grad():
+            mod.weight.copy_(1 + 0.2 * torch.randn(C, generator=g))
+            mod.bias.copy_(0.1 * torch.randn(C, generator=g))
+        return mod.to(gpu)
+    ln, gn = (lambda: affine(torch.nn.LayerNorm(C))), (lambda: affine(torch.nn.GroupNorm(32, C)))
+    if form == "ln_lin":
+        return ("lin", rnd(M, C), (rnd(Co, C, scale=C ** -0.5), rnd(Co)), None, ("ln", ln(), 1e-5), rnd(M, Co),
+                (rnd(frames, Co), HW), rnd(M, Co))
+    if form == "gn_silu_c3":
+        from gcd_amd import autograd_ops as A
+        return ("c3", rnd(M, C), (rnd(Co, C, 3, 3, scale=(9 * C) ** -0.5), rnd(Co)), A._c3_geo(frames, H, W),
+                ("gn", gn(), HW, 1e-5, True), rnd(M, Co), (rnd(frames, Co), HW), rnd(M, Co))
+    if form == "gn_t3":
+        return ("t3", rnd(M, C), (rnd(C, C, 3, 1, 1, scale=(3 * C) ** -0.5), None), dict(T=T, HW=HW),
+                ("gn", gn(), T * HW, 1e-5, True), rnd(M, C), None, rnd(M, C))
+    if form == "geglu_lin":
+        return "lin", rnd(M, 2 * C), (rnd(Co, C, scale=C ** -0.5), None), None, ("geglu",), rnd(M, Co), None, rnd(M, Co)
+    assert form == "ln_qkv"
+    return ("qkv", rnd(M, C), tuple(rnd(Co, C, scale=C ** -0.5) for _ in range(3)), None, ("ln", ln(), 1e-5), None, None,
+            rnd(M, 3 * Co))
+
+
+@pytest.fixture(params=[False, True], ids=["default", "deterministic"])
+def reduction_mode(request):
+    from gcd_amd import autograd_ops as A
+    old = A.DETERMINISTIC
+    A.set_deterministic(request.param)
+    yield request.param
+    A.set_deterministic(old)
+
+
+@pytest.mark.parametrize("form", ["ln_lin", "gn_silu_c3", "gn_t3", "geglu_lin", "ln_qkv"])
+def test_operator_core_equals_fused_apply(gpu, form, reduction_mode):
+    """autograd_ops.fused_forward / fused_backward called directly (what the planned engine does) against Fused.apply +
+    torch.autograd.grad on the same inputs: the same kernels on the same operands, so bit-equal — but for the outputs
+    of the atomic fp32 sums of the default mode (db, d_vec, dgamma, dbeta of the LayerNorm forms), which are held to
+    max(10 x the run-to-run spread of Fused.apply itself, 1e-6) rel-L2, the rule of tests/memcontract.py.  In the
+    deterministic mode nothing is excepted."""
+    from gcd_amd import autograd_ops as A
+    A.PACK.clear()
+    kind, x, params, geo, norm, res, rowvec, dy = _core_form(form, gpu)
+    spec, gamma, beta = A._spec(kind, geo, norm, rowvec)
+    vec = None if rowvec is None else rowvec[0]
+    names = ["dx", "d_res", "d_vec", "dgamma", "dbeta"] + (["dwq", "dwk", "dwv"] if kind == "qkv" else ["dw", "db"])
+
+    def tape():
+        leaves = [None if t is None else t.detach().clone().requires_grad_(True)
+                  for t in (x, res, vec, gamma, beta, *params)]
+        y = A.Fused.apply(spec, *leaves)
+        wanted = [t for t in leaves if t is not None]
+        grads = iter(torch.autograd.grad(y, wanted, dy))
+        return y.detach(), [None if t is None else next(grads) for t in leaves]
+    y_ref, g_ref = tape()
+    _, g_again = tape()
+    y, saved = A.fused_forward(spec, x, res, vec, None if gamma is None else gamma.detach(),
+                               None if beta is None else beta.detach(), params)
+    dx, d_res, d_vec, dgamma, dbeta, dps = A.fused_backward(
+        saved, dy, need_x=True, need_res=True, need_vec=True, need_norm=True, need_params=[p is not None for p in params])
+    torch.cuda.synchronize()
+    assert torch.equal(y, y_ref)
+    atomic = ("db", "d_vec", "dgamma", "dbeta") if norm[0] == "ln" and not reduction_mode else ()
+    for name, got, ref, again in zip(names, [dx, d_res, d_vec, dgamma, dbeta, *dps], g_ref, g_again):
+        assert (got is None) == (ref is None), name
+        if ref is None:
+            continue
+        got = got.reshape(ref.shape)
+        if name in atomic:
+            spread, err = rel_l2(again, ref), rel_l2(got, ref)
+            print(f"  {form} {name}: run-to-run spread of Fused.apply {spread:.2e}, core vs Fused.apply {err:.2e}")
+            assert err <= max(10 * spread, 1e-6), (name, err, spread)
+        else:
+            assert torch.equal(got, ref), f"{form} {name}: rel-L2 {rel_l2(got, ref):.2e}"
+
+
+def test_operator_core_qkv_leaves_the_gemm_in_fp16(gpu):
+    """ln -> q|k|v with geo out16 (the planned engine's form, forward only): the fp32 form's result rounded to fp16."""
+    from gcd_amd import autograd_ops as A
+    A.PACK.clear()
+    kind, x, params, _, norm, _, _, _ = _core_form("ln_qkv", gpu)
+    spec32, gamma, beta = A._spec(kind, None, norm, None)
+    spec16, _, _ = A._spec(kind, dict(out16=True), norm, None)
+    y32, _ = A.fused_forward(spec32, x, None, None, gamma.detach(), beta.detach(), params)
+    y16, _ = A.fused_forward(spec16, x, None, None, gamma.detach(), beta.detach(), params)
+    assert y16.dtype == torch.float16 and y32.dtype == torch.float32
+    assert torch.equal(y16, y32.half())
+
+
+def test_attention_cores_equal_their_autograd_functions(gpu):
+    """spatial / temporal_attention_forward + _backward against SpatialAttention / TemporalAttention.apply + autograd: the
+    Functions return the fp32 image of the core's fp16 result, and the same dqkv."""
+    from gcd_amd import autograd_ops as A
+    g = _gen(53)
+    for fwd, bwd, fn, dims in [
+            (A.spatial_attention_forward, A.spatial_attention_backward, A.SpatialAttention, (2, 64, 1)),
+            (A.temporal_attention_forward, A.temporal_attention_backward, A.TemporalAttention, (1, 3, 16, 1))]:
+        M = math.prod(dims[:-1])
+        qkv = torch.randn(M, 3 * 64 * dims[-1], generator=g).to(gpu)
+        dO = torch.randn(M, 64 * dims[-1], generator=g).to(gpu)
+        leaf = qkv.clone().requires_grad_(True)
+        y_ref = fn.apply(leaf, *dims)
+        (d_ref,) = torch.autograd.grad(y_ref, leaf, dO)
+        o16, saved = fwd(qkv, *dims)
+        dqkv = bwd(saved, dO)
+        torch.cuda.synchronize()
+        assert o16.dtype == torch.float16 and torch.equal(o16.float(), y_ref.detach()), fn.__name__
+        assert torch.equal(dqkv, d_ref), f"{fn.__name__}: rel-L2 {rel_l2(dqkv, d_ref):.2e}"

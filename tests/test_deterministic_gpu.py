@@ -175,7 +175,7 @@ def test_two_plans_alternating_are_bit_equal(gpu, det):
             assert torch.equal(got[n], ref[n]), n
     ids_a, ids_b = {id(p) for p in na.parameters()}, {id(p) for p in nb.parameters()}
     assert heard and all(id(p) in ids_a for p in heard) and not any(id(p) in ids_b for p in heard)
-    assert A._sink() is None
+    assert not hasattr(A._SCOPE, "sink")
 
 
 @pytest.mark.parametrize("engine", ["planned", "autograd"])

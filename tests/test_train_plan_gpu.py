@@ -473,7 +473,7 @@ def test_two_plans_alternating_in_one_process_do_not_interfere(gpu):
     assert worst[1] <= max(10 * spread, 1e-6)
     ids_a, ids_b = {id(p) for p in na.parameters()}, {id(p) for p in nb.parameters()}
     assert heard and all(id(p) in ids_a for p in heard) and not any(id(p) in ids_b for p in heard)
-    assert A._sink() is None
+    assert not hasattr(A._SCOPE, "sink")
 
 
 def test_planned_engine_inputs_that_need_gradients_and_no_grad_forwards(gpu):

@@ -466,13 +466,26 @@ def test_train_engine_switch_and_planned_engine_refuse_loudly():
     assert not any("_gcd_grad_listeners" in p.__dict__ for p in net.parameters())
     with pytest.raises(ValueError):
         TR.TrainDenoiser({"target": "gcd_amd.denoiser_scaling.VScalingWithEDMcNoise"}, engine="planed")
-    # the in-place gradient sink and the fp16 pass-through are per-thread scopes, restored on exit
-    assert A._sink() is None
-    with A.grad_sink("plan-a"):
-        with A.grad_sink("plan-b"):
-            assert A._sink() == "plan-b"
-        assert A._sink() == "plan-a"
-    assert A._sink() is None
+    # a plan's gradient destination is visible only to its own backward: the sink is an ARGUMENT of the backward helpers, and
+    # `_sink_dest` answers from the sink it is handed alone (no ambient state)
+    assert not hasattr(A, "grad_sink") and not hasattr(A, "_sink")
+    flat = torch.zeros(64)
+    q, k, v, w, other = (torch.zeros(2, 4) for _ in range(5))
+
+    class Sink:
+        views = {id(q): flat[0:8].view(2, 4), id(k): flat[8:16].view(2, 4), id(v): flat[16:24].view(2, 4),
+                 id(w): flat[32:40].view(2, 4)}
+
+        def grad_dest(self, p):
+            return self.views.get(id(p))
+    assert A._sink_dest(None, q) is None
+    (d,) = A._sink_dest(Sink(), q)
+    assert d.data_ptr() == flat.data_ptr() and d.shape == q.shape
+    ds = A._sink_dest(Sink(), q, k, v)                                   # q | k | v back to back: one destination
+    assert [t.data_ptr() - flat.data_ptr() for t in ds] == [0, 32, 64]
+    assert A._sink_dest(Sink(), q, k, w) is None                         # a gap between two of them
+    assert A._sink_dest(Sink(), other) is None and A._sink_dest(Sink(), q, other) is None   # not this sink's parameter
+    # the fp16 pass-through is a per-thread scope, restored on exit
     d = A._f16_passthrough_on()
     with A.f16_passthrough(not d):
         assert A._f16_passthrough_on() == (not d)
@@ -490,3 +503,73 @@ def test_checkpoint_policy_is_a_memory_decision():
     assert TrainPlan.contexts_fit(t2, 320, 60 * GB) and not TrainPlan.contexts_fit(t8, 320, 60 * GB)
     assert not TrainPlan.contexts_fit(t8, 320, 80 * GB - 30 * GB)
     assert not TrainPlan.contexts_fit(112 * 64 * 96, 320, 280 * GB)
+
+
+def test_reduction_dispatch_states_each_argument_list_once(monkeypatch):
+    """autograd_ops._reduction: default mode -> the default entry with args + (stream,); deterministic mode -> the `_det`
+    entry of the training library with args + (scratch_ptr, scratch_floats, stream), counted in DET_CALLS, refused when the
+    entry needs more scratch than the training workspace holds."""
+    from gcd_amd import _lib, autograd_ops as A
+
+    class Lib:
+        def __init__(self):
+            self.calls = []
+
+        def __getattr__(self, name):
+            return lambda *a: self.calls.append((name, a)) or 0
+    dflt, train, checked = Lib(), Lib(), []
+    ws = torch.zeros(100)
+    monkeypatch.setattr(A, "_stream", lambda: 77)
+    monkeypatch.setattr(A, "_train_ws", lambda device: ws)
+    monkeypatch.setattr(_lib, "load_train", lambda: train)
+    monkeypatch.setattr(_lib, "check_train", lambda rc, what: checked.append(("train", rc, what)))
+    monkeypatch.setattr(A, "DET_CALLS", {})
+    need = []
+
+    def run(floats):
+        A._reduction((lambda: dflt, lambda rc, what: checked.append(("default", rc, what)), "gcd_x"), "gcd_x_det",
+                     lambda lib: need.append(lib) or floats, "cpu", (1, 2.5, 3))
+    monkeypatch.setattr(A, "DETERMINISTIC", False)
+    run(40)
+    assert dflt.calls == [("gcd_x", (1, 2.5, 3, 77))] and not train.calls and not need and not A.DET_CALLS
+    assert checked == [("default", 0, "gcd_x")]
+    monkeypatch.setattr(A, "DETERMINISTIC", True)
+    run(40)
+    run(100)                                                  # exactly the workspace: still fits
+    assert len(dflt.calls) == 1 and need == [train, train]
+    assert train.calls == [("gcd_x_det", (1, 2.5, 3, ws.data_ptr(), 100, 77))] * 2
+    assert A.DET_CALLS == {"gcd_x_det": 2} and checked[1:] == [("train", 0, "gcd_x_det")] * 2
+    with pytest.raises(_lib.GcdError, match="gcd_x_det: needs 101 floats"):
+        run(101)
+    assert len(train.calls) == 2 and A.DET_CALLS == {"gcd_x_det": 2}
+
+
+def test_deterministic_signatures_are_the_default_ones_plus_scratch():
+    """What _reduction rests on: each deterministic entry takes its default entry's arguments with (scratch, scratch_floats)
+    in front of the stream."""
+    import ctypes as C
+    from gcd_amd import _lib
+    pairs = [(_lib.SIGNATURES, "gcd_rowblock_sum_f32", "gcd_rowblock_sum_det_f32"),
+             (_lib.SIGNATURES, "gcd_cast_colsum_f32", "gcd_cast_colsum_det_f32"),
+             (_lib.SIGNATURES, "gcd_layernorm_bwd", "gcd_layernorm_bwd_det"),
+             (_lib.TRAIN_SIGNATURES, "gcd_blend_bwd_f32", "gcd_blend_bwd_det_f32"),
+             (_lib.TRAIN_SIGNATURES, "gcd_smallm_dgrad", "gcd_smallm_dgrad_det")]
+    for table, name, det in pairs:
+        (res, args), (dres, dargs) = table[name], _lib.TRAIN_DET_SIGNATURES[det]
+        assert dres is res and list(dargs) == list(args[:-1]) + [C.c_void_p, C.c_int64, args[-1]], (name, det)
+
+
+def test_planned_engine_calls_the_operator_core_not_a_forged_ctx():
+    """train_plan.py has no stand-in for torch's ctx and calls no static method of the tape engine's Functions."""
+    import ast
+    import gcd_amd.train_plan as TP
+    tree = ast.parse(Path(TP.__file__).read_text())
+    assert not [n for n in ast.walk(tree) if isinstance(n, ast.ClassDef) and n.name == "_Ctx"]
+    bad = []
+    for n in ast.walk(tree):
+        if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr in ("forward", "backward"):
+            f = n.func.value
+            if isinstance(f, ast.Attribute) and isinstance(f.value, ast.Name) and f.value.id == "A" and \
+                    f.attr in ("Fused", "SpatialAttention", "TemporalAttention"):
+                bad.append((f.attr, n.func.attr, n.lineno))
+    assert not bad, bad
