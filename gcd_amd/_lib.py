@@ -78,9 +78,11 @@ SIGNATURES = {
     "gcd_ff_packed_bytes": (_i64, []),
     "gcd_ff_pack_f16": (_i, [_vp, _vp, _vp, _i, _vp]),
     "gcd_ff_fused_supported": (_i, [_i, _i, _i]),
+    "gcd_ff_fused_fits": (_i, [_i64, _i, _i, _i64, _i]),
     "gcd_ff_fused_f16": (_i, [C.POINTER(FfDesc), _vp]),
     "gcd_lnqkv_packed_bytes": (_i64, [_i]),
     "gcd_lnqkv_supported": (_i, [_i, _i]),
+    "gcd_lnqkv_fits": (_i, [_i, _i, _i64, _i64]),
     "gcd_lnqkv_pack_f16": (_i, [_vp, _i, _vp, _vp]),
     "gcd_lnqkv_f16": (_i, [_vp, _i64, _vp, _vp, _f, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "gcd_groupnorm_stats_from_colsums": (_i, [_vp, _i, _vp, _i, _i64, _i64, _f, _vp, _vp]),

@@ -17,8 +17,21 @@ extern "C" int gcd_ff_pack_f16(const void* w1, const void* w2, void* wp, int for
   return 0;
 }
 
-extern "C" int gcd_ff_fused_supported(int M, int C, int hidden) {
-  return M >= 1 && C == FF_C && hidden == FF_HID;
+// The result leaves through ONE buffer descriptor over `out` whose num_records and byte offsets are 32-bit ints
+// (ff_fused_kernel.h: rsrcO, store_cb): num_records = M ldo es, and the largest offset formed — dropped by the range check,
+// but formed — is that of the last overhang row of the last 128-token tile, ((Mpad - 1) ldo + FF_C - 4) es.  Both must be
+// <= INT_MAX.  In divisions, so that nothing here can overflow either.
+static bool ff_out_fits(int64_t M, int64_t ldo, int out_kind) {
+  const int64_t lim = (int64_t)0x7fffffff / (out_kind == GCD_OUT_F16 ? 2 : 4);      // in elements
+  if (M < 1 || M > lim || ldo < FF_C || ldo > lim) return false;
+  const int64_t mpad = (M + 127) / 128 * 128;
+  return M <= lim / ldo && mpad - 1 <= (lim - (FF_C - 4)) / ldo;
+}
+
+extern "C" int gcd_ff_fused_supported(int M, int C, int hidden) { return M >= 1 && C == FF_C && hidden == FF_HID; }
+
+extern "C" int gcd_ff_fused_fits(int64_t M, int C, int hidden, int64_t ldo, int out_kind) {
+  return C == FF_C && hidden == FF_HID && (out_kind == GCD_OUT_F32 || out_kind == GCD_OUT_F16) && ff_out_fits(M, ldo, out_kind);
 }
 
 namespace {
@@ -69,6 +82,9 @@ extern "C" int gcd_ff_fused_f16(const gcd_ff_desc* d, void* stream) {
                 "gcd_ff_fused_f16: R2 rows must be 16-byte aligned");
   GCD_CHECK_ARG(d->out_kind == GCD_OUT_F32 || d->out_kind == GCD_OUT_F16, "gcd_ff_fused_f16: out_kind %d", d->out_kind);
   GCD_CHECK_ARG(d->ldo >= FF_C && d->ldo % 4 == 0 && ((uintptr_t)d->out & 15) == 0, "gcd_ff_fused_f16: out rows must be 16-byte aligned");
+  GCD_CHECK_ARG(ff_out_fits(d->M, d->ldo, d->out_kind),
+                "gcd_ff_fused_f16: out of M = %d rows (+ the last tile's overhang) x ldo = %lld %s exceeds the 32-bit buffer offsets "
+                "(2^31 - 1 bytes)", d->M, (long long)d->ldo, d->out_kind == GCD_OUT_F16 ? "fp16" : "fp32");
   GCD_CHECK_ARG(((uintptr_t)d->wp & 15) == 0 && ((uintptr_t)d->b1 & 15) == 0 && ((uintptr_t)d->b2 & 15) == 0,
                 "gcd_ff_fused_f16: wp / b1 / b2 must be 16-byte aligned");
   GCD_CHECK_ARG(!d->frame_alpha || (d->rows_per_alpha > 0 && d->rows_per_alpha % 32 == 0),

@@ -243,6 +243,12 @@ extern "C" int64_t gcd_lnqkv_packed_bytes(int N) { return N > 0 && N % 64 == 0 ?
 
 extern "C" int gcd_lnqkv_supported(int C, int N) { return C == LQ_C && N > 0 && N % 64 == 0 && N <= 4096; }
 
+// the size-aware form: the result leaves through one buffer descriptor with 32-bit byte offsets (gcd_lnqkv_f16's own check)
+extern "C" int gcd_lnqkv_fits(int C, int N, int64_t M, int64_t ldo) {
+  const int64_t lim = ((int64_t)0x7fffffff - 1) / 2;      // M ldo 2 < 0x7fffffff, in elements
+  return gcd_lnqkv_supported(C, N) && M >= 1 && ldo >= N && ldo <= lim && M <= lim / ldo;
+}
+
 extern "C" int gcd_lnqkv_pack_f16(const void* W, int N, void* wp, void* stream) {
   GCD_CHECK_ARG(W && wp, "gcd_lnqkv_pack_f16: null pointer");
   GCD_CHECK_ARG(gcd_lnqkv_supported(LQ_C, N), "gcd_lnqkv_pack_f16: N=%d (a multiple of 64, <= 4096)", N);
@@ -261,8 +267,8 @@ extern "C" int gcd_lnqkv_f16(const float* x32, int64_t ldx32, const float* gamma
   GCD_CHECK_ARG(ldx32 >= C && ldx32 % 4 == 0 && ((uintptr_t)x32 & 15) == 0, "gcd_lnqkv_f16: x32 rows must be 16-byte aligned");
   GCD_CHECK_ARG(ldo >= N && ldo % 8 == 0 && ((uintptr_t)out16 & 15) == 0, "gcd_lnqkv_f16: out rows must be 16-byte aligned");
   GCD_CHECK_ARG(((uintptr_t)wp & 15) == 0, "gcd_lnqkv_f16: wp must be 16-byte aligned");
-  GCD_CHECK_ARG((int64_t)M * ldo * 2 < (int64_t)0x7fffffff, "gcd_lnqkv_f16: output of %lld bytes exceeds the 32-bit buffer offsets",
-                (long long)((int64_t)M * ldo * 2));
+  GCD_CHECK_ARG(gcd_lnqkv_fits(C, N, M, ldo), "gcd_lnqkv_f16: output of M = %d rows x ldo = %lld fp16 exceeds the 32-bit buffer offsets "
+                "(M ldo 2 < 2^31 - 1 bytes)", M, (long long)ldo);
   LnQkvK k;
   k.x32 = x32;
   k.ldx32 = ldx32;

@@ -481,11 +481,12 @@ class UNetEngine:
                addvec=None, rows_per_vec=1) -> bool:
         """x = ff(norm(x32 + addvec)) + (x32 + addvec) [blended with r2] as ONE launch (ff_fused_kernel.h, the LayerNorm
         form): the LayerNorm kernel, its fp16 output and the 660 MB hidden tensor never touch memory.  False = not taken
-        (another level, too few tokens, switched off): the caller runs LayerNorm + two GEMMs."""
+        (another level, too few tokens, an `out` beyond the kernel's 32-bit offsets, switched off): the caller runs
+        LayerNorm + two GEMMs."""
         # (a frame of H * W % 32 != 0 tokens with a per-frame vector / blend factor goes the LayerNorm + two-GEMM way)
         if "wp" not in F or self.fuse_layernorm or not ops.ff_fused_ok(
                 M, F["w1"].shape[1], F["w1"].shape[0] // 2, rows_per_vec=None if addvec is None else rows_per_vec,
-                rows_per_alpha=None if frame_alpha is None else rows_per_alpha):
+                rows_per_alpha=None if frame_alpha is None else rows_per_alpha, ldo=out.stride(0), out_kind=out_kind):
             return False
         ln = dict(gamma=affine[0], beta=affine[1], addvec=addvec, rows_per_vec=rows_per_vec)
         kw = dict(r2=r2, out_kind=out_kind, frame_alpha=frame_alpha, rows_per_alpha=rows_per_alpha, ln=ln)
@@ -496,11 +497,12 @@ class UNetEngine:
 
     def _ln_qkv(self, A, x32, affine, M) -> torch.Tensor:
         """q | k | v = to_qkv(norm1(x32)) as fp16 [M, 3 C]: ONE launch where the model width is 320 and the tile count pays
-        (lnqkv.hip: the fp32 rows are read once, the normalised operand never reaches memory), else LayerNorm + GEMM."""
+        (lnqkv.hip: the fp32 rows are read once, the normalised operand never reaches memory), else — also where q | k | v
+        reaches the 2^31 bytes of that kernel's 32-bit output offsets — LayerNorm + GEMM."""
         ws = self.ws
         N3 = A["wqkv"].shape[0]
         qkv = ws.alloc((M, N3), torch.float16)
-        if "wqkv_p" in A and not self.fuse_layernorm and ops.lnqkv_ok(M, A["wqkv"].shape[1], N3):
+        if "wqkv_p" in A and not self.fuse_layernorm and ops.lnqkv_ok(M, A["wqkv"].shape[1], N3, ldo=qkv.stride(0)):
             sched = self._next_dir() if _ZIGZAG in (1, 2) else 0
             ops.lnqkv(x32, affine[0], affine[1], A["wqkv_p"], qkv, M=M, N=N3, sched=sched)
             return qkv

@@ -241,13 +241,16 @@ FF_FUSED_MIN_TOKENS = int(os.environ.get("GCD_FF_FUSED_MIN_TOKENS", str(4 * 256 
 
 
 def ff_fused_ok(M: int, C_: int, hidden: int, enabled: Optional[bool] = None, rows_per_vec: Optional[int] = None,
-                rows_per_alpha: Optional[int] = None) -> bool:
+                rows_per_alpha: Optional[int] = None, ldo: Optional[int] = None, out_kind: int = OUT_F32) -> bool:
     """rows_per_vec / rows_per_alpha: the per-frame geometry of a call with `addvec` / `frame_alpha` (None: not used).
-    gcd_ff_fused_f16 takes one vector / blend factor per 32-row wave tile and refuses anything else."""
+    gcd_ff_fused_f16 takes one vector / blend factor per 32-row wave tile and refuses anything else.
+    ldo / out_kind: row stride (None: C_, a compact result) and kind of `out`, which the kernel addresses with 32-bit byte
+    offsets: False where M rows of it — the last 128-token tile's overhang included — would pass 2^31 - 1 bytes."""
     on = _FF_FUSED_ON if enabled is None else enabled
     if (rows_per_vec is not None and rows_per_vec % 32) or (rows_per_alpha is not None and rows_per_alpha % 32):
         return False
-    return bool(on and M >= FF_FUSED_MIN_TOKENS and _lib.load().gcd_ff_fused_supported(M, C_, hidden))
+    return bool(on and M >= FF_FUSED_MIN_TOKENS and _lib.load().gcd_ff_fused_fits(
+        M, C_, hidden, C_ if ldo is None else ldo, out_kind))
 
 
 def ff_pack(w1_geglu16: torch.Tensor, w2_16: torch.Tensor, for_ln: bool = False) -> torch.Tensor:
@@ -303,9 +306,11 @@ _LNQKV_ON = os.environ.get("GCD_LNQKV", "1") != "0"
 LNQKV_MIN_TOKENS = int(os.environ.get("GCD_LNQKV_MIN_TOKENS", str(2 * 256 * 256)))
 
 
-def lnqkv_ok(M: int, C_: int, N: int, enabled: Optional[bool] = None) -> bool:
+def lnqkv_ok(M: int, C_: int, N: int, enabled: Optional[bool] = None, ldo: Optional[int] = None) -> bool:
+    """ldo: row stride of the fp16 result (None: N, compact).  False where M rows of it reach 2^31 - 1 bytes: the kernel
+    addresses its output with 32-bit byte offsets (gcd_lnqkv_fits)."""
     on = _LNQKV_ON if enabled is None else enabled
-    return bool(on and M >= LNQKV_MIN_TOKENS and _lib.load().gcd_lnqkv_supported(C_, N))
+    return bool(on and M >= LNQKV_MIN_TOKENS and _lib.load().gcd_lnqkv_fits(C_, N, M, N if ldo is None else ldo))
 
 
 def lnqkv_pack(w16: torch.Tensor) -> torch.Tensor:

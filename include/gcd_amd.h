@@ -246,6 +246,12 @@ int64_t gcd_ff_packed_bytes(void);
  * for the LayerNorm form (W1's K order follows the channel strips of the accumulator layout x32 is read in).        */
 int gcd_ff_pack_f16(const void* w1, const void* w2, void* wp, int for_ln, void* stream);
 int gcd_ff_fused_supported(int M, int C, int hidden);
+/* The same with the size limit of `out`, the one operand that leaves through a buffer descriptor with 32-bit byte offsets
+ * (an addition to ABI v9; gcd_ff_fused_supported keeps answering for the shape alone): M ldo es and the offset of the last
+ * overhang row of the last 128-token tile, ((Mpad - 1) ldo + 316) es, both <= 2^31 - 1 (es = 4 for GCD_OUT_F32, 2 for
+ * GCD_OUT_F16).  gcd_ff_fused_f16 refuses exactly where this says no; x32, X, R1 and R2 are read through 64-bit pointers
+ * and have no limit. */
+int gcd_ff_fused_fits(int64_t M, int C, int hidden, int64_t ldo, int out_kind);
 int gcd_ff_fused_f16(const gcd_ff_desc* desc, void* stream);
 
 /* ---- LayerNorm + q | k | v projection as one launch where the model width is 320 (ABI v9) ------------------------------
@@ -258,6 +264,9 @@ int gcd_ff_fused_f16(const gcd_ff_desc* desc, void* stream);
  * 256-token tiles from the end (pure scheduling, as gcd_gemm_desc.sched).                                                  */
 int64_t gcd_lnqkv_packed_bytes(int N);
 int gcd_lnqkv_supported(int C, int N);
+/* The same with the size limit of the result, which leaves through a buffer descriptor with 32-bit byte offsets (an
+ * addition to ABI v9): M ldo 2 < 2^31 - 1.  gcd_lnqkv_f16 refuses exactly where this says no. */
+int gcd_lnqkv_fits(int C, int N, int64_t M, int64_t ldo);
 int gcd_lnqkv_pack_f16(const void* W, int N, void* wp, void* stream);
 int gcd_lnqkv_f16(const float* x32, int64_t ldx32, const float* gamma, const float* beta, float eps, const void* wp,
                   void* out16, int64_t ldo, int M, int C, int N, int sched, void* stream);
