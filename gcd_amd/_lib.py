@@ -228,8 +228,44 @@ TRAIN_OPTIM_SIGNATURES = {
     "gcd_ema_update": (_i, [_vp, _i, _i64, C.POINTER(OptimConfig), _vp, _vp]),
 }
 
+# libgcd_amd_sampler.so (include/gcd_amd_sampler.h; gcd_amd/csrc/sampler_stage.hip): the stage kernel of the sampler family
+SAMPLER_LIB_PATH = _PKG / "libgcd_amd_sampler.so"
+SAMPLER_ABI_VERSION = 1
+SAMPLER_ROW = 12          # floats per row of the coefficient table
+SAMPLER_SIGNATURES = {
+    "gcd_sampler_abi_version": (_i, []),
+    "gcd_sampler_last_error": (C.c_char_p, []),
+    "gcd_sampler_stage_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp]),
+}
+
 _lib = None
 _train = None
+_sampler = None
+
+
+def load_sampler() -> C.CDLL:
+    """Load libgcd_amd_sampler.so (once).  Raises if it has not been built — never falls back."""
+    global _sampler
+    if _sampler is not None:
+        return _sampler
+    if not SAMPLER_LIB_PATH.exists():
+        raise GcdError(f"{SAMPLER_LIB_PATH} is missing: run `python -m gcd_amd.csrc.build` (needs hipcc)")
+    lib = C.CDLL(str(SAMPLER_LIB_PATH))
+    for name, (res, args) in SAMPLER_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.gcd_sampler_abi_version()
+    if v != SAMPLER_ABI_VERSION:
+        raise GcdError(f"libgcd_amd_sampler ABI version {v} != expected {SAMPLER_ABI_VERSION}; rebuild the library")
+    _sampler = lib
+    return lib
+
+
+def check_sampler(rc: int, what: str = "") -> None:
+    if rc != 0:
+        msg = load_sampler().gcd_sampler_last_error().decode(errors="replace")
+        raise GcdError(f"{what or 'libgcd_amd_sampler call'} failed (status {rc}): {msg}")
 
 
 def load_train() -> C.CDLL:

@@ -33,6 +33,12 @@ STAMP_TRAIN = PKG / ".libgcd_amd_train.stamp"
 TRAIN_SOURCES = ["train_wgrad.hip", "train_ops.hip", "train_det.hip", "train_optim.hip"]
 TRAIN_HEADERS = [ROOT / "include" / "gcd_amd_train.h", ROOT / "include" / "gcd_amd_train_det.h",
                  ROOT / "include" / "gcd_amd_train_optim.h", CSRC / "train_wgrad_kernel.h"]
+# libgcd_amd_sampler.so: the stage kernel of the sampler family (include/gcd_amd_sampler.h).  Not part of `SOURCES`,
+# `HEADERS` or `sources_digest()` either: the Euler step that the traffic profile describes never launches it.
+LIB_SAMPLER = PKG / "libgcd_amd_sampler.so"
+STAMP_SAMPLER = PKG / ".libgcd_amd_sampler.stamp"
+SAMPLER_SOURCES = ["sampler_stage.hip"]
+SAMPLER_HEADERS = [ROOT / "include" / "gcd_amd_sampler.h"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast"]
@@ -92,6 +98,34 @@ def build_train(force: bool = False, verbose: bool = True) -> Path:
     return LIB_TRAIN
 
 
+def build_sampler(force: bool = False, verbose: bool = True) -> Path:
+    """gcd_amd/libgcd_amd_sampler.so (the sampler-stage kernel), in-tree like the other two libraries."""
+    h = hashlib.sha256()
+    for p in [CSRC / s for s in SAMPLER_SOURCES] + SAMPLER_HEADERS:
+        h.update(p.read_bytes())
+    h.update(" ".join(FLAGS).encode())
+    digest = h.hexdigest()
+    if not force and LIB_SAMPLER.exists() and STAMP_SAMPLER.exists() and STAMP_SAMPLER.read_text().strip() == digest:
+        return LIB_SAMPLER
+    hipcc = _hipcc()
+    objdir = CSRC / "build"
+    objdir.mkdir(exist_ok=True)
+    objs = []
+    for src in SAMPLER_SOURCES:
+        obj = objdir / (src + ".o")
+        cmd = [hipcc, *FLAGS, "-c", str(CSRC / src), "-o", str(obj)]
+        if verbose:
+            print("[gcd_amd.build]", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=str(objdir))
+        objs.append(str(obj))
+    cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", str(LIB_SAMPLER)]
+    if verbose:
+        print("[gcd_amd.build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    STAMP_SAMPLER.write_text(digest)
+    return LIB_SAMPLER
+
+
 def build(force: bool = False, save_temps: bool = False, verbose: bool = True,
           ablation: bool = False) -> Path:
     """ablation=True builds tools/libgcd_amd_ablate.so instead: the same sources with
@@ -100,6 +134,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True,
     if ablation:
         return _build_ablation(verbose)
     build_train(force=force, verbose=verbose)
+    build_sampler(force=force, verbose=verbose)
     digest = _digest()
     if not force and LIB.exists() and STAMP.exists() and STAMP.read_text().strip() == digest:
         return LIB
