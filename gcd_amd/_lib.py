@@ -238,9 +238,50 @@ SAMPLER_SIGNATURES = {
     "gcd_sampler_stage_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp]),
 }
 
+# libgcd_amd_metrics.so (include/gcd_amd_metrics.h; gcd_amd/csrc/metrics.hip): the evaluation metrics on the device
+METRICS_LIB_PATH = _PKG / "libgcd_amd_metrics.so"
+METRICS_ABI_VERSION = 1
+METRICS_SIGNED = 1             # flags bit 0: pred is the decoder's raw output in [-1, 1]
+METRICS_FRAME_VALUES = 6       # psnr, ssim, psnr_vis, ssim_vis, psnr_occ, ssim_occ
+METRICS_DIVERSITY_VALUES = 3   # all, visible, occluded
+METRICS_SIGNATURES = {
+    "gcd_metrics_abi_version": (_i, []),
+    "gcd_metrics_last_error": (C.c_char_p, []),
+    "gcd_metrics_frames_scratch_bytes": (_i64, [_i, _i, _i, _i]),
+    "gcd_metrics_diversity_scratch_bytes": (_i64, [_i, _i, _i, _i]),
+    "gcd_metrics_frames_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp]),
+    "gcd_metrics_diversity_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp]),
+}
+
 _lib = None
 _train = None
 _sampler = None
+_metrics = None
+
+
+def load_metrics() -> C.CDLL:
+    """Load libgcd_amd_metrics.so (once).  Raises if it has not been built — never falls back."""
+    global _metrics
+    if _metrics is not None:
+        return _metrics
+    if not METRICS_LIB_PATH.exists():
+        raise GcdError(f"{METRICS_LIB_PATH} is missing: run `python -m gcd_amd.csrc.build` (needs hipcc)")
+    lib = C.CDLL(str(METRICS_LIB_PATH))
+    for name, (res, args) in METRICS_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.gcd_metrics_abi_version()
+    if v != METRICS_ABI_VERSION:
+        raise GcdError(f"libgcd_amd_metrics ABI version {v} != expected {METRICS_ABI_VERSION}; rebuild the library")
+    _metrics = lib
+    return lib
+
+
+def check_metrics(rc: int, what: str = "") -> None:
+    if rc != 0:
+        msg = load_metrics().gcd_metrics_last_error().decode(errors="replace")
+        raise GcdError(f"{what or 'libgcd_amd_metrics call'} failed (status {rc}): {msg}")
 
 
 def load_sampler() -> C.CDLL:

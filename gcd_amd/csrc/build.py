@@ -39,6 +39,12 @@ LIB_SAMPLER = PKG / "libgcd_amd_sampler.so"
 STAMP_SAMPLER = PKG / ".libgcd_amd_sampler.stamp"
 SAMPLER_SOURCES = ["sampler_stage.hip"]
 SAMPLER_HEADERS = [ROOT / "include" / "gcd_amd_sampler.h"]
+# libgcd_amd_metrics.so: the evaluation metrics on the device (include/gcd_amd_metrics.h).  Outside `sources_digest()`
+# like the two above: no kernel of a sampler step is launched differently because of it.
+LIB_METRICS = PKG / "libgcd_amd_metrics.so"
+STAMP_METRICS = PKG / ".libgcd_amd_metrics.stamp"
+METRICS_SOURCES = ["metrics.hip"]
+METRICS_HEADERS = [ROOT / "include" / "gcd_amd_metrics.h"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast"]
@@ -126,6 +132,34 @@ def build_sampler(force: bool = False, verbose: bool = True) -> Path:
     return LIB_SAMPLER
 
 
+def build_metrics(force: bool = False, verbose: bool = True) -> Path:
+    """gcd_amd/libgcd_amd_metrics.so (the device-resident evaluation metrics), in-tree like the other libraries."""
+    h = hashlib.sha256()
+    for p in [CSRC / s for s in METRICS_SOURCES] + METRICS_HEADERS:
+        h.update(p.read_bytes())
+    h.update(" ".join(FLAGS).encode())
+    digest = h.hexdigest()
+    if not force and LIB_METRICS.exists() and STAMP_METRICS.exists() and STAMP_METRICS.read_text().strip() == digest:
+        return LIB_METRICS
+    hipcc = _hipcc()
+    objdir = CSRC / "build"
+    objdir.mkdir(exist_ok=True)
+    objs = []
+    for src in METRICS_SOURCES:
+        obj = objdir / (src + ".o")
+        cmd = [hipcc, *FLAGS, "-c", str(CSRC / src), "-o", str(obj)]
+        if verbose:
+            print("[gcd_amd.build]", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=str(objdir))
+        objs.append(str(obj))
+    cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", str(LIB_METRICS)]
+    if verbose:
+        print("[gcd_amd.build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    STAMP_METRICS.write_text(digest)
+    return LIB_METRICS
+
+
 def build(force: bool = False, save_temps: bool = False, verbose: bool = True,
           ablation: bool = False) -> Path:
     """ablation=True builds tools/libgcd_amd_ablate.so instead: the same sources with
@@ -135,6 +169,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True,
         return _build_ablation(verbose)
     build_train(force=force, verbose=verbose)
     build_sampler(force=force, verbose=verbose)
+    build_metrics(force=force, verbose=verbose)
     digest = _digest()
     if not force and LIB.exists() and STAMP.exists() and STAMP.read_text().strip() == digest:
         return LIB
