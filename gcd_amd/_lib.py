@@ -253,10 +253,65 @@ METRICS_SIGNATURES = {
     "gcd_metrics_diversity_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp]),
 }
 
+# libgcd_amd_render.so (include/gcd_amd_render.h; gcd_amd/csrc/render.hip): point clouds to (source, target) frames
+RENDER_LIB_PATH = _PKG / "libgcd_amd_render.so"
+RENDER_ABI_VERSION = 1
+RENDER_F16, RENDER_F32, RENDER_F64, RENDER_U8 = 0, 1, 2, 3      # element types of the cloud
+RENDER_MAX_CAMERAS = 8
+RENDER_CAM_DOUBLES = 25        # K (3 x 3) then RT (4 x 4), row-major
+RENDER_MAX_KERNEL = 31
+
+
+class RenderSplatDesc(C.Structure):
+    """gcd_render_splat_desc (include/gcd_amd_render.h)."""
+    _fields_ = [("xyz", _vp), ("rgb", _vp), ("xyz_ld", _i64), ("rgb_ld", _i64), ("N", _i64),
+                ("xyz_dtype", C.c_int32), ("rgb_dtype", C.c_int32), ("cams", _vp),
+                ("nc", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("spread_radius", C.c_int32),
+                ("img", _vp), ("img_cs", _i64), ("img_ld", _i64),
+                ("weights", _vp), ("weights_cs", _i64), ("weights_ld", _i64),
+                ("uv", _vp), ("depth", _vp), ("status", _vp), ("scratch", _vp), ("scratch_bytes", _i64)]
+
+
+_d = C.c_double
+RENDER_SIGNATURES = {
+    "gcd_render_abi_version": (_i, []),
+    "gcd_render_last_error": (C.c_char_p, []),
+    "gcd_render_scratch_bytes": (_i64, [_i, _i, _i]),
+    "gcd_render_fill_scratch_bytes": (_i64, [_i, _i]),
+    "gcd_render_splat": (_i, [C.POINTER(RenderSplatDesc), _vp]),
+    "gcd_render_fill_resize_f32": (_i, [_vp, _i64, _i, _i, _i, _d, _vp, _i64, _i64, _i64, _i, _i, _d, _d, _vp, _i64, _vp]),
+}
+
 _lib = None
 _train = None
 _sampler = None
 _metrics = None
+_render = None
+
+
+def load_render() -> C.CDLL:
+    """Load libgcd_amd_render.so (once).  Raises if it has not been built — never falls back."""
+    global _render
+    if _render is not None:
+        return _render
+    if not RENDER_LIB_PATH.exists():
+        raise GcdError(f"{RENDER_LIB_PATH} is missing: run `python -m gcd_amd.csrc.build` (needs hipcc)")
+    lib = C.CDLL(str(RENDER_LIB_PATH))
+    for name, (res, args) in RENDER_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.gcd_render_abi_version()
+    if v != RENDER_ABI_VERSION:
+        raise GcdError(f"libgcd_amd_render ABI version {v} != expected {RENDER_ABI_VERSION}; rebuild the library")
+    _render = lib
+    return lib
+
+
+def check_render(rc: int, what: str = "") -> None:
+    if rc != 0:
+        msg = load_render().gcd_render_last_error().decode(errors="replace")
+        raise GcdError(f"{what or 'libgcd_amd_render call'} failed (status {rc}): {msg}")
 
 
 def load_metrics() -> C.CDLL:

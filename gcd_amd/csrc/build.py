@@ -45,6 +45,12 @@ LIB_METRICS = PKG / "libgcd_amd_metrics.so"
 STAMP_METRICS = PKG / ".libgcd_amd_metrics.stamp"
 METRICS_SOURCES = ["metrics.hip"]
 METRICS_HEADERS = [ROOT / "include" / "gcd_amd_metrics.h"]
+# libgcd_amd_render.so: point clouds to (source, target) frames (include/gcd_amd_render.h).  Outside `sources_digest()` like
+# the three above: it produces the data of a step and launches nothing inside one.
+LIB_RENDER = PKG / "libgcd_amd_render.so"
+STAMP_RENDER = PKG / ".libgcd_amd_render.stamp"
+RENDER_SOURCES = ["render.hip"]
+RENDER_HEADERS = [ROOT / "include" / "gcd_amd_render.h"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast"]
@@ -160,6 +166,34 @@ def build_metrics(force: bool = False, verbose: bool = True) -> Path:
     return LIB_METRICS
 
 
+def build_render(force: bool = False, verbose: bool = True) -> Path:
+    """gcd_amd/libgcd_amd_render.so (the point-cloud renderer of the data stage), in-tree like the other libraries."""
+    h = hashlib.sha256()
+    for p in [CSRC / s for s in RENDER_SOURCES] + RENDER_HEADERS:
+        h.update(p.read_bytes())
+    h.update(" ".join(FLAGS).encode())
+    digest = h.hexdigest()
+    if not force and LIB_RENDER.exists() and STAMP_RENDER.exists() and STAMP_RENDER.read_text().strip() == digest:
+        return LIB_RENDER
+    hipcc = _hipcc()
+    objdir = CSRC / "build"
+    objdir.mkdir(exist_ok=True)
+    objs = []
+    for src in RENDER_SOURCES:
+        obj = objdir / (src + ".o")
+        cmd = [hipcc, *FLAGS, "-c", str(CSRC / src), "-o", str(obj)]
+        if verbose:
+            print("[gcd_amd.build]", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=str(objdir))
+        objs.append(str(obj))
+    cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", str(LIB_RENDER)]
+    if verbose:
+        print("[gcd_amd.build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    STAMP_RENDER.write_text(digest)
+    return LIB_RENDER
+
+
 def build(force: bool = False, save_temps: bool = False, verbose: bool = True,
           ablation: bool = False) -> Path:
     """ablation=True builds tools/libgcd_amd_ablate.so instead: the same sources with
@@ -170,6 +204,12 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True,
     build_train(force=force, verbose=verbose)
     build_sampler(force=force, verbose=verbose)
     build_metrics(force=force, verbose=verbose)
+    # a partial copy of the tree without the renderer's source (the clean-tree tests of the other libraries make one)
+    # builds the rest; nothing stands in for the library then: `_lib.load_render()` raises where it is asked for
+    if all((CSRC / s).exists() for s in RENDER_SOURCES):
+        build_render(force=force, verbose=verbose)
+    elif verbose:
+        print(f"[gcd_amd.build] {RENDER_SOURCES} not in {CSRC}: {LIB_RENDER.name} is NOT built", flush=True)
     digest = _digest()
     if not force and LIB.exists() and STAMP.exists() and STAMP.read_text().strip() == digest:
         return LIB
