@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 from pathlib import Path
+from typing import Callable, NamedTuple
 
 import os
 
@@ -282,137 +283,66 @@ RENDER_SIGNATURES = {
     "gcd_render_fill_resize_f32": (_i, [_vp, _i64, _i, _i, _i, _d, _vp, _i64, _i64, _i64, _i, _i, _d, _d, _vp, _i64, _vp]),
 }
 
-_lib = None
-_train = None
-_sampler = None
-_metrics = None
-_render = None
+
+class Binding(NamedTuple):
+    """One shared object of the project: where it is, which ABI version it must report, the entries that report the
+    version and the last error, the signature table(s) of everything its header(s) declare, and its loader and check."""
+    name: str
+    path: Path
+    abi_version: int
+    version_entry: str
+    error_entry: str
+    tables: tuple
+    load: Callable[[], C.CDLL]
+    check: Callable[..., None]
 
 
-def load_render() -> C.CDLL:
-    """Load libgcd_amd_render.so (once).  Raises if it has not been built — never falls back."""
-    global _render
-    if _render is not None:
-        return _render
-    if not RENDER_LIB_PATH.exists():
-        raise GcdError(f"{RENDER_LIB_PATH} is missing: run `python -m gcd_amd.csrc.build` (needs hipcc)")
-    lib = C.CDLL(str(RENDER_LIB_PATH))
-    for name, (res, args) in RENDER_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.gcd_render_abi_version()
-    if v != RENDER_ABI_VERSION:
-        raise GcdError(f"libgcd_amd_render ABI version {v} != expected {RENDER_ABI_VERSION}; rebuild the library")
-    _render = lib
-    return lib
+def _bind(name: str, path: Path, abi_version: int, version_entry: str, error_entry: str, *tables: dict) -> Binding:
+    """`load` and `check` are plain functions over this call's cells: the tape fine-tune engine calls each of them about
+    10^4 times per step."""
+    cdll = None
+
+    def load() -> C.CDLL:
+        """Load the library (once per process).  Raises if it has not been built — never falls back."""
+        nonlocal cdll
+        if cdll is not None:
+            return cdll
+        if not path.exists():
+            raise GcdError(f"{path} is missing: the HIP library has not been built. "
+                           "Run `python -m gcd_amd.csrc.build` (needs hipcc); gcd_amd has no CPU fallback.")
+        lib = C.CDLL(str(path))
+        for table in tables:
+            for entry, (res, args) in table.items():
+                fn = getattr(lib, entry)  # AttributeError if the .so does not export a declared symbol
+                fn.restype = res
+                fn.argtypes = args
+        v = getattr(lib, version_entry)()
+        if v != abi_version:
+            raise GcdError(f"lib{name} ABI version {v} != expected {abi_version}; rebuild the library")
+        cdll = lib
+        return lib
+
+    def check(rc: int, what: str = "") -> None:
+        if rc != 0:
+            msg = getattr(load(), error_entry)().decode(errors="replace")
+            raise GcdError(f"{what or 'lib' + name + ' call'} failed (status {rc}): {msg}")
+
+    return Binding(name, path, abi_version, version_entry, error_entry, tables, load, check)
 
 
-def check_render(rc: int, what: str = "") -> None:
-    if rc != 0:
-        msg = load_render().gcd_render_last_error().decode(errors="replace")
-        raise GcdError(f"{what or 'libgcd_amd_render call'} failed (status {rc}): {msg}")
-
-
-def load_metrics() -> C.CDLL:
-    """Load libgcd_amd_metrics.so (once).  Raises if it has not been built — never falls back."""
-    global _metrics
-    if _metrics is not None:
-        return _metrics
-    if not METRICS_LIB_PATH.exists():
-        raise GcdError(f"{METRICS_LIB_PATH} is missing: run `python -m gcd_amd.csrc.build` (needs hipcc)")
-    lib = C.CDLL(str(METRICS_LIB_PATH))
-    for name, (res, args) in METRICS_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.gcd_metrics_abi_version()
-    if v != METRICS_ABI_VERSION:
-        raise GcdError(f"libgcd_amd_metrics ABI version {v} != expected {METRICS_ABI_VERSION}; rebuild the library")
-    _metrics = lib
-    return lib
-
-
-def check_metrics(rc: int, what: str = "") -> None:
-    if rc != 0:
-        msg = load_metrics().gcd_metrics_last_error().decode(errors="replace")
-        raise GcdError(f"{what or 'libgcd_amd_metrics call'} failed (status {rc}): {msg}")
-
-
-def load_sampler() -> C.CDLL:
-    """Load libgcd_amd_sampler.so (once).  Raises if it has not been built — never falls back."""
-    global _sampler
-    if _sampler is not None:
-        return _sampler
-    if not SAMPLER_LIB_PATH.exists():
-        raise GcdError(f"{SAMPLER_LIB_PATH} is missing: run `python -m gcd_amd.csrc.build` (needs hipcc)")
-    lib = C.CDLL(str(SAMPLER_LIB_PATH))
-    for name, (res, args) in SAMPLER_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.gcd_sampler_abi_version()
-    if v != SAMPLER_ABI_VERSION:
-        raise GcdError(f"libgcd_amd_sampler ABI version {v} != expected {SAMPLER_ABI_VERSION}; rebuild the library")
-    _sampler = lib
-    return lib
-
-
-def check_sampler(rc: int, what: str = "") -> None:
-    if rc != 0:
-        msg = load_sampler().gcd_sampler_last_error().decode(errors="replace")
-        raise GcdError(f"{what or 'libgcd_amd_sampler call'} failed (status {rc}): {msg}")
-
-
-def load_train() -> C.CDLL:
-    """Load libgcd_amd_train.so (once).  Raises if it has not been built — never falls back."""
-    global _train
-    if _train is not None:
-        return _train
-    if not TRAIN_LIB_PATH.exists():
-        raise GcdError(f"{TRAIN_LIB_PATH} is missing: run `python -m gcd_amd.csrc.build` (needs hipcc)")
-    lib = C.CDLL(str(TRAIN_LIB_PATH))
-    for name, (res, args) in (list(TRAIN_SIGNATURES.items()) + list(TRAIN_DET_SIGNATURES.items())
-                              + list(TRAIN_OPTIM_SIGNATURES.items())):
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.gcd_train_abi_version()
-    if v != TRAIN_ABI_VERSION:
-        raise GcdError(f"libgcd_amd_train ABI version {v} != expected {TRAIN_ABI_VERSION}; rebuild the library")
-    _train = lib
-    return lib
-
-
-def check_train(rc: int, what: str = "") -> None:
-    if rc != 0:
-        msg = load_train().gcd_train_last_error().decode(errors="replace")
-        raise GcdError(f"{what or 'libgcd_amd_train call'} failed (status {rc}): {msg}")
-
-
-def load() -> C.CDLL:
-    """Load libgcd_amd.so (once).  Raises if it has not been built — never falls back."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not LIB_PATH.exists():
-        raise GcdError(
-            f"{LIB_PATH} is missing: the HIP extension has not been built. "
-            "Run `python -m gcd_amd.csrc.build` (needs hipcc); gcd_amd has no CPU fallback."
-        )
-    lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.gcd_abi_version()
-    if v != ABI_VERSION:
-        raise GcdError(f"libgcd_amd ABI version {v} != expected {ABI_VERSION}; rebuild the library")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str = "") -> None:
-    if rc != 0:
-        msg = load().gcd_last_error().decode(errors="replace")
-        raise GcdError(f"{what or 'libgcd_amd call'} failed (status {rc}): {msg}")
+BINDINGS = {b.name: b for b in (
+    _bind("gcd_amd", LIB_PATH, ABI_VERSION, "gcd_abi_version", "gcd_last_error", SIGNATURES),
+    _bind("gcd_amd_train", TRAIN_LIB_PATH, TRAIN_ABI_VERSION, "gcd_train_abi_version", "gcd_train_last_error",
+          TRAIN_SIGNATURES, TRAIN_DET_SIGNATURES, TRAIN_OPTIM_SIGNATURES),
+    _bind("gcd_amd_sampler", SAMPLER_LIB_PATH, SAMPLER_ABI_VERSION, "gcd_sampler_abi_version", "gcd_sampler_last_error",
+          SAMPLER_SIGNATURES),
+    _bind("gcd_amd_metrics", METRICS_LIB_PATH, METRICS_ABI_VERSION, "gcd_metrics_abi_version", "gcd_metrics_last_error",
+          METRICS_SIGNATURES),
+    _bind("gcd_amd_render", RENDER_LIB_PATH, RENDER_ABI_VERSION, "gcd_render_abi_version", "gcd_render_last_error",
+          RENDER_SIGNATURES),
+)}
+load, check = BINDINGS["gcd_amd"].load, BINDINGS["gcd_amd"].check
+load_train, check_train = BINDINGS["gcd_amd_train"].load, BINDINGS["gcd_amd_train"].check
+load_sampler, check_sampler = BINDINGS["gcd_amd_sampler"].load, BINDINGS["gcd_amd_sampler"].check
+load_metrics, check_metrics = BINDINGS["gcd_amd_metrics"].load, BINDINGS["gcd_amd_metrics"].check
+load_render, check_render = BINDINGS["gcd_amd_render"].load, BINDINGS["gcd_amd_render"].check

@@ -1,8 +1,8 @@
-"""Build libgcd_amd.so (the C-ABI HIP library) in-tree with hipcc for gfx950.
+"""Build the project's HIP libraries (C ABI, one shared object each) in-tree with hipcc for gfx950.
 
 Usage: python -m gcd_amd.csrc.build [--force] [--save-temps]
-The shared object lands next to the package (gcd_amd/libgcd_amd.so) so that it travels with the
-source tree to the GPU box (it is git-ignored, not gpurun-ignored).
+The shared objects land next to the package (gcd_amd/libgcd_amd*.so), inside the source tree, and are git-ignored.
+`LIBRARIES` is where a new library is added.
 """
 from __future__ import annotations
 
@@ -11,13 +11,14 @@ import os
 import shutil
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
+from typing import NamedTuple
 
 CSRC = Path(__file__).resolve().parent
 PKG = CSRC.parent
 ROOT = PKG.parent
-LIB = PKG / "libgcd_amd.so"
-STAMP = PKG / ".libgcd_amd.stamp"
+INCLUDE = ROOT / "include"
 SOURCES = ["runtime.hip", "gemm.hip", "gemm_pp.hip", "gemm_p8.hip", "conv_narrow.hip", "ff_fused.hip", "lnqkv.hip", "norm.hip", "attention.hip",
            "attn_temporal_long.hip", "attn_bwd.hip", "elementwise.hip", "backward.hip"]
 # per-source extra flags.  ff_fused.hip: hipcc's SLP pass pairs the GELU polynomial's scalar FMAs into v_pk_fma_f32, which
@@ -25,35 +26,48 @@ SOURCES = ["runtime.hip", "gemm.hip", "gemm_pp.hip", "gemm_p8.hip", "conv_narrow
 EXTRA_FLAGS = {"ff_fused.hip": ["-fno-slp-vectorize"]}
 # records of experiments that lost their A/B: compiled into the ablation / A-B libraries only (tools/libgcd_amd_*.so)
 ABLATION_ONLY_SOURCES = ["gemm_p8x.hip"]
-HEADERS = [CSRC / "common.h", CSRC / "gemm_common.h", CSRC / "ff_fused_kernel.h", ROOT / "include" / "gcd_amd.h"]
-# libgcd_amd_train.so: kernels of the fine-tune step only (include/gcd_amd_train.h).  Its sources are NOT part of
-# `sources_digest()`: they cannot change a kernel the sampler step launches.
-LIB_TRAIN = PKG / "libgcd_amd_train.so"
-STAMP_TRAIN = PKG / ".libgcd_amd_train.stamp"
-TRAIN_SOURCES = ["train_wgrad.hip", "train_ops.hip", "train_det.hip", "train_optim.hip"]
-TRAIN_HEADERS = [ROOT / "include" / "gcd_amd_train.h", ROOT / "include" / "gcd_amd_train_det.h",
-                 ROOT / "include" / "gcd_amd_train_optim.h", CSRC / "train_wgrad_kernel.h"]
-# libgcd_amd_sampler.so: the stage kernel of the sampler family (include/gcd_amd_sampler.h).  Not part of `SOURCES`,
-# `HEADERS` or `sources_digest()` either: the Euler step that the traffic profile describes never launches it.
-LIB_SAMPLER = PKG / "libgcd_amd_sampler.so"
-STAMP_SAMPLER = PKG / ".libgcd_amd_sampler.stamp"
-SAMPLER_SOURCES = ["sampler_stage.hip"]
-SAMPLER_HEADERS = [ROOT / "include" / "gcd_amd_sampler.h"]
-# libgcd_amd_metrics.so: the evaluation metrics on the device (include/gcd_amd_metrics.h).  Outside `sources_digest()`
-# like the two above: no kernel of a sampler step is launched differently because of it.
-LIB_METRICS = PKG / "libgcd_amd_metrics.so"
-STAMP_METRICS = PKG / ".libgcd_amd_metrics.stamp"
-METRICS_SOURCES = ["metrics.hip"]
-METRICS_HEADERS = [ROOT / "include" / "gcd_amd_metrics.h"]
-# libgcd_amd_render.so: point clouds to (source, target) frames (include/gcd_amd_render.h).  Outside `sources_digest()` like
-# the three above: it produces the data of a step and launches nothing inside one.
-LIB_RENDER = PKG / "libgcd_amd_render.so"
-STAMP_RENDER = PKG / ".libgcd_amd_render.stamp"
-RENDER_SOURCES = ["render.hip"]
-RENDER_HEADERS = [ROOT / "include" / "gcd_amd_render.h"]
+HEADERS = [CSRC / "common.h", CSRC / "gemm_common.h", CSRC / "ff_fused_kernel.h", INCLUDE / "gcd_amd.h"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast"]
+MAX_JOBS = 16      # compiler processes at a time
+
+
+class Library(NamedTuple):
+    """One shared object: gcd_amd/lib<name>.so, current while gcd_amd/.lib<name>.stamp holds its digest."""
+    name: str
+    sources: list      # file names under CSRC
+    headers: list      # paths: every header whose change must rebuild the library
+    extra_flags: dict  # source -> flags added to FLAGS for that source
+
+    @property
+    def so(self) -> Path:
+        return PKG / f"lib{self.name}.so"
+
+    @property
+    def stamp(self) -> Path:
+        return PKG / f".lib{self.name}.stamp"
+
+
+# Only the first entry is part of `sources_digest()`: no source of the others can change a kernel that a sampler step
+# launches (the Euler step that the traffic profile describes never launches the stage kernel either; the metrics and the
+# renderer produce and judge the data of a step and launch nothing inside one).
+LIBRARIES = {lib.name: lib for lib in (
+    Library("gcd_amd", SOURCES, HEADERS, EXTRA_FLAGS),
+    # kernels of the fine-tune step only
+    Library("gcd_amd_train", ["train_wgrad.hip", "train_ops.hip", "train_det.hip", "train_optim.hip"],
+            [INCLUDE / "gcd_amd_train.h", INCLUDE / "gcd_amd_train_det.h", INCLUDE / "gcd_amd_train_optim.h",
+             CSRC / "train_wgrad_kernel.h", CSRC / "train_common.h"], {}),
+    # the stage kernel of the sampler family
+    Library("gcd_amd_sampler", ["sampler_stage.hip"], [INCLUDE / "gcd_amd_sampler.h"], {}),
+    # the evaluation metrics on the device
+    Library("gcd_amd_metrics", ["metrics.hip"], [INCLUDE / "gcd_amd_metrics.h"], {}),
+    # point clouds to (source, target) frames
+    Library("gcd_amd_render", ["render.hip"], [INCLUDE / "gcd_amd_render.h"], {}),
+)}
+MAIN = LIBRARIES["gcd_amd"]
+LIB = MAIN.so
+STAMP = MAIN.stamp
 
 
 def _hipcc() -> str:
@@ -63,12 +77,12 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (looked at $HIPCC, PATH and /opt/rocm/bin/hipcc)")
 
 
-def _digest() -> str:
+def _digest(lib: Library = MAIN) -> str:
     h = hashlib.sha256()
-    for p in [CSRC / s for s in SOURCES] + HEADERS:
+    for p in [CSRC / s for s in lib.sources] + lib.headers:
         h.update(p.read_bytes())
     h.update(" ".join(FLAGS).encode())
-    h.update(repr(sorted(EXTRA_FLAGS.items())).encode())
+    h.update(repr(sorted(lib.extra_flags.items())).encode())
     return h.hexdigest()      # (ABLATION_ONLY_SOURCES are not in the product library)
 
 
@@ -82,116 +96,39 @@ def sources_digest() -> str:
     return h.hexdigest()[:16]
 
 
-def build_train(force: bool = False, verbose: bool = True) -> Path:
-    """gcd_amd/libgcd_amd_train.so (the fine-tune step's own kernels), in-tree like the main library."""
-    h = hashlib.sha256()
-    for p in [CSRC / s for s in TRAIN_SOURCES] + TRAIN_HEADERS:
-        h.update(p.read_bytes())
-    h.update(" ".join(FLAGS).encode())
-    digest = h.hexdigest()
-    if not force and LIB_TRAIN.exists() and STAMP_TRAIN.exists() and STAMP_TRAIN.read_text().strip() == digest:
-        return LIB_TRAIN
+def _compile_and_link(sources, out: Path, objdir: Path, extra_flags, defines=(), save_temps: bool = False,
+                      verbose: bool = True) -> Path:
+    """hipcc over `sources` (at most MAX_JOBS at a time) into `objdir`, then one link into `out`."""
     hipcc = _hipcc()
-    objdir = CSRC / "build"
-    objdir.mkdir(exist_ok=True)
-    objs = []
-    for src in TRAIN_SOURCES:
-        obj = objdir / (src + ".o")
-        cmd = [hipcc, *FLAGS, "-c", str(CSRC / src), "-o", str(obj)]
+    objdir.mkdir(parents=True, exist_ok=True)
+
+    def run(cmd, what, **kw):
         if verbose:
             print("[gcd_amd.build]", " ".join(cmd), flush=True)
-        subprocess.check_call(cmd, cwd=str(objdir))
-        objs.append(str(obj))
-    cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", str(LIB_TRAIN)]
-    if verbose:
-        print("[gcd_amd.build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    STAMP_TRAIN.write_text(digest)
-    return LIB_TRAIN
+        if subprocess.call(cmd, **kw) != 0:
+            raise RuntimeError(f"hipcc failed on {what}")
 
-
-def build_sampler(force: bool = False, verbose: bool = True) -> Path:
-    """gcd_amd/libgcd_amd_sampler.so (the sampler-stage kernel), in-tree like the other two libraries."""
-    h = hashlib.sha256()
-    for p in [CSRC / s for s in SAMPLER_SOURCES] + SAMPLER_HEADERS:
-        h.update(p.read_bytes())
-    h.update(" ".join(FLAGS).encode())
-    digest = h.hexdigest()
-    if not force and LIB_SAMPLER.exists() and STAMP_SAMPLER.exists() and STAMP_SAMPLER.read_text().strip() == digest:
-        return LIB_SAMPLER
-    hipcc = _hipcc()
-    objdir = CSRC / "build"
-    objdir.mkdir(exist_ok=True)
-    objs = []
-    for src in SAMPLER_SOURCES:
+    def compile_one(src):
         obj = objdir / (src + ".o")
-        cmd = [hipcc, *FLAGS, "-c", str(CSRC / src), "-o", str(obj)]
-        if verbose:
-            print("[gcd_amd.build]", " ".join(cmd), flush=True)
-        subprocess.check_call(cmd, cwd=str(objdir))
-        objs.append(str(obj))
-    cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", str(LIB_SAMPLER)]
-    if verbose:
-        print("[gcd_amd.build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    STAMP_SAMPLER.write_text(digest)
-    return LIB_SAMPLER
+        temps = ["-save-temps=obj"] if save_temps else []
+        run([hipcc, *temps, *FLAGS, *extra_flags.get(src, []), *defines, "-c", str(CSRC / src), "-o", str(obj)], src,
+            cwd=str(objdir))
+        return str(obj)
+
+    with ThreadPoolExecutor(max_workers=MAX_JOBS) as pool:
+        objs = list(pool.map(compile_one, sources))
+    run([hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", str(out)], out.name)
+    return out
 
 
-def build_metrics(force: bool = False, verbose: bool = True) -> Path:
-    """gcd_amd/libgcd_amd_metrics.so (the device-resident evaluation metrics), in-tree like the other libraries."""
-    h = hashlib.sha256()
-    for p in [CSRC / s for s in METRICS_SOURCES] + METRICS_HEADERS:
-        h.update(p.read_bytes())
-    h.update(" ".join(FLAGS).encode())
-    digest = h.hexdigest()
-    if not force and LIB_METRICS.exists() and STAMP_METRICS.exists() and STAMP_METRICS.read_text().strip() == digest:
-        return LIB_METRICS
-    hipcc = _hipcc()
-    objdir = CSRC / "build"
-    objdir.mkdir(exist_ok=True)
-    objs = []
-    for src in METRICS_SOURCES:
-        obj = objdir / (src + ".o")
-        cmd = [hipcc, *FLAGS, "-c", str(CSRC / src), "-o", str(obj)]
-        if verbose:
-            print("[gcd_amd.build]", " ".join(cmd), flush=True)
-        subprocess.check_call(cmd, cwd=str(objdir))
-        objs.append(str(obj))
-    cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", str(LIB_METRICS)]
-    if verbose:
-        print("[gcd_amd.build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    STAMP_METRICS.write_text(digest)
-    return LIB_METRICS
-
-
-def build_render(force: bool = False, verbose: bool = True) -> Path:
-    """gcd_amd/libgcd_amd_render.so (the point-cloud renderer of the data stage), in-tree like the other libraries."""
-    h = hashlib.sha256()
-    for p in [CSRC / s for s in RENDER_SOURCES] + RENDER_HEADERS:
-        h.update(p.read_bytes())
-    h.update(" ".join(FLAGS).encode())
-    digest = h.hexdigest()
-    if not force and LIB_RENDER.exists() and STAMP_RENDER.exists() and STAMP_RENDER.read_text().strip() == digest:
-        return LIB_RENDER
-    hipcc = _hipcc()
-    objdir = CSRC / "build"
-    objdir.mkdir(exist_ok=True)
-    objs = []
-    for src in RENDER_SOURCES:
-        obj = objdir / (src + ".o")
-        cmd = [hipcc, *FLAGS, "-c", str(CSRC / src), "-o", str(obj)]
-        if verbose:
-            print("[gcd_amd.build]", " ".join(cmd), flush=True)
-        subprocess.check_call(cmd, cwd=str(objdir))
-        objs.append(str(obj))
-    cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", str(LIB_RENDER)]
-    if verbose:
-        print("[gcd_amd.build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    STAMP_RENDER.write_text(digest)
-    return LIB_RENDER
+def build_library(lib: Library, force: bool = False, save_temps: bool = False, verbose: bool = True) -> Path:
+    """Bring one library up to date: a no-op while its stamp holds the digest of its sources, headers and flags."""
+    digest = _digest(lib)
+    if not force and lib.so.exists() and lib.stamp.exists() and lib.stamp.read_text().strip() == digest:
+        return lib.so
+    _compile_and_link(lib.sources, lib.so, CSRC / "build", lib.extra_flags, save_temps=save_temps, verbose=verbose)
+    lib.stamp.write_text(digest)
+    return lib.so
 
 
 def build(force: bool = False, save_temps: bool = False, verbose: bool = True,
@@ -201,66 +138,18 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True,
     (GCD_TUNE_GEMM_IMPL >= 32).  The product library never contains them."""
     if ablation:
         return _build_ablation(verbose)
-    build_train(force=force, verbose=verbose)
-    build_sampler(force=force, verbose=verbose)
-    build_metrics(force=force, verbose=verbose)
-    # a partial copy of the tree without the renderer's source (the clean-tree tests of the other libraries make one)
-    # builds the rest; nothing stands in for the library then: `_lib.load_render()` raises where it is asked for
-    if all((CSRC / s).exists() for s in RENDER_SOURCES):
-        build_render(force=force, verbose=verbose)
-    elif verbose:
-        print(f"[gcd_amd.build] {RENDER_SOURCES} not in {CSRC}: {LIB_RENDER.name} is NOT built", flush=True)
-    digest = _digest()
-    if not force and LIB.exists() and STAMP.exists() and STAMP.read_text().strip() == digest:
-        return LIB
-    hipcc = _hipcc()
-    objdir = CSRC / "build"
-    objdir.mkdir(exist_ok=True)
-    procs = []
-    for src in SOURCES:
-        obj = objdir / (src + ".o")
-        cmd = [hipcc, *FLAGS, *EXTRA_FLAGS.get(src, []), "-c", str(CSRC / src), "-o", str(obj)]
-        if save_temps:
-            cmd.insert(1, "-save-temps=obj")
-        if verbose:
-            print("[gcd_amd.build]", " ".join(cmd), flush=True)
-        procs.append((src, obj, subprocess.Popen(cmd, cwd=str(objdir))))
-    objs = []
-    for src, obj, pr in procs:
-        if pr.wait() != 0:
-            raise RuntimeError(f"hipcc failed on {src}")
-        objs.append(str(obj))
-    cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", str(LIB)]
-    if verbose:
-        print("[gcd_amd.build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    STAMP.write_text(digest)
+    for lib in LIBRARIES.values():
+        build_library(lib, force=force, save_temps=save_temps, verbose=verbose)
     return LIB
 
 
 def _build_ablation(verbose: bool, name: str = "ablate", defines=("-DGCD_ABLATION_BUILD",)) -> Path:
     """A second library beside the product one (tools/libgcd_amd_<name>.so) from the same sources with extra defines:
     the ablation build, and the A/B variants of tools/ab_sweep.sh (loaded through GCD_AMD_LIB, see _lib.py)."""
-    hipcc = _hipcc()
-    objdir = CSRC / "build" / name
-    objdir.mkdir(parents=True, exist_ok=True)
-    out = ROOT / "tools" / f"libgcd_amd_{name}.so"
-    procs = []
     if "-DGCD_ABLATION_BUILD" not in defines:
         defines = tuple(defines) + ("-DGCD_ABLATION_BUILD",)      # every A/B library carries the ablation-only variants
-    for src in SOURCES + ABLATION_ONLY_SOURCES:
-        obj = objdir / (src + ".o")
-        cmd = [hipcc, *FLAGS, *EXTRA_FLAGS.get(src, []), *defines, "-c", str(CSRC / src), "-o", str(obj)]
-        if verbose:
-            print("[gcd_amd.build]", " ".join(cmd), flush=True)
-        procs.append((src, obj, subprocess.Popen(cmd, cwd=str(objdir))))
-    objs = []
-    for src, obj, pr in procs:
-        if pr.wait() != 0:
-            raise RuntimeError(f"hipcc failed on {src}")
-        objs.append(str(obj))
-    subprocess.check_call([hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", str(out)])
-    return out
+    return _compile_and_link(SOURCES + ABLATION_ONLY_SOURCES, ROOT / "tools" / f"libgcd_amd_{name}.so", CSRC / "build" / name,
+                             EXTRA_FLAGS, defines=defines, verbose=verbose)
 
 
 if __name__ == "__main__":

@@ -15,32 +15,16 @@
 #include <stdint.h>
 
 #include "../../include/gcd_amd_train_det.h"
+#include "train_common.h"
 
 typedef _Float16 f16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef unsigned short us8 __attribute__((ext_vector_type(8)));
 
-void gcd_train_set_error(const char* fmt, ...);      // train_wgrad.hip
-
-#define D_CHECK_ARG(cond, ...)          \
-  do {                                  \
-    if (!(cond)) {                      \
-      gcd_train_set_error(__VA_ARGS__); \
-      return 2;                         \
-    }                                   \
-  } while (0)
-#define D_CHECK_LAUNCH(what)                                                     \
-  do {                                                                           \
-    hipError_t e_ = hipGetLastError();                                           \
-    if (e_ != hipSuccess) {                                                      \
-      gcd_train_set_error("%s: launch failed: %s", what, hipGetErrorString(e_)); \
-      return 1;                                                                  \
-    }                                                                            \
-  } while (0)
-#define D_CHECK_SCRATCH(what, need)                                                                                   \
-  D_CHECK_ARG(scratch && scratch_floats >= (need) && ((uintptr_t)scratch & 15) == 0,                                  \
-              "%s: scratch of %lld floats, need %lld (%s_scratch_floats), 16-byte aligned", what, (long long)scratch_floats, \
-              (long long)(need), what)
+#define CHECK_SCRATCH(what, need)                                                                                   \
+  CHECK_ARG(scratch && scratch_floats >= (need) && ((uintptr_t)scratch & 15) == 0,                                  \
+            "%s: scratch of %lld floats, need %lld (%s_scratch_floats), 16-byte aligned", what, (long long)scratch_floats, \
+            (long long)(need), what)
 
 namespace {
 
@@ -511,21 +495,21 @@ extern "C" int64_t gcd_rowblock_sum_det_scratch_floats(int64_t M, int N, int64_t
 
 extern "C" int gcd_rowblock_sum_det_f32(const float* x, int64_t ldx, int64_t M, int N, int64_t rows_per_block, float* out,
                                         float* scratch, int64_t scratch_floats, void* stream) {
-  D_CHECK_ARG(x && out && M > 0 && N > 0 && rows_per_block > 0 && M % rows_per_block == 0,
-              "gcd_rowblock_sum_det_f32: M=%lld rows_per_block=%lld", (long long)M, (long long)rows_per_block);
-  D_CHECK_ARG(N % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0,
-              "gcd_rowblock_sum_det_f32: N=%d / ldx=%lld must be multiples of 4, x 16-byte aligned", N, (long long)ldx);
+  CHECK_ARG(x && out && M > 0 && N > 0 && rows_per_block > 0 && M % rows_per_block == 0,
+            "gcd_rowblock_sum_det_f32: M=%lld rows_per_block=%lld", (long long)M, (long long)rows_per_block);
+  CHECK_ARG(N % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0,
+            "gcd_rowblock_sum_det_f32: N=%d / ldx=%lld must be multiples of 4, x 16-byte aligned", N, (long long)ldx);
   const int64_t nblk = M / rows_per_block;
-  D_CHECK_ARG(nblk <= 65535, "gcd_rowblock_sum_det_f32: too many blocks");
-  D_CHECK_SCRATCH("gcd_rowblock_sum_det", gcd_rowblock_sum_det_scratch_floats(M, N, rows_per_block));
+  CHECK_ARG(nblk <= 65535, "gcd_rowblock_sum_det_f32: too many blocks");
+  CHECK_SCRATCH("gcd_rowblock_sum_det", gcd_rowblock_sum_det_scratch_floats(M, N, rows_per_block));
   const int nsplit = rowblock_nsplit(rows_per_block);
   hipLaunchKernelGGL(rowblock_partial_kernel, dim3((N + 255) / 256, (unsigned)nblk, (unsigned)nsplit), dim3(256), 0,
                      (hipStream_t)stream, x, ldx, rows_per_block, N, scratch);
-  D_CHECK_LAUNCH("gcd_rowblock_sum_det_f32");
+  CHECK_LAUNCH("gcd_rowblock_sum_det_f32");
   const int64_t total = nblk * N;
   hipLaunchKernelGGL(fold_groups_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scratch,
                      nsplit, N, total, out);
-  D_CHECK_LAUNCH("gcd_rowblock_sum_det_f32 (fold)");
+  CHECK_LAUNCH("gcd_rowblock_sum_det_f32 (fold)");
   return 0;
 }
 
@@ -538,18 +522,18 @@ extern "C" int gcd_layernorm_bwd_det(const float* x, int64_t ldx, const float* d
                                      const float* gamma, float eps, float* dx, int64_t lddx, float* dgamma, float* dbeta,
                                      const float* dx_add, int64_t ld_add, float* scratch, int64_t scratch_floats,
                                      void* stream) {
-  D_CHECK_ARG(!dx_add || ld_add % 4 == 0, "gcd_layernorm_bwd_det: ld_add");
-  D_CHECK_ARG(x && dy && gamma && dx && dgamma && dbeta, "gcd_layernorm_bwd_det: null pointer");
-  D_CHECK_ARG(C > 0 && C % 4 == 0 && C <= 1280 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && M > 0,
-              "gcd_layernorm_bwd_det: C=%d (multiple of 4, <= 1280), leading dimensions multiples of 4", C);
-  D_CHECK_SCRATCH("gcd_layernorm_bwd_det", gcd_layernorm_bwd_det_scratch_floats(M, C));
+  CHECK_ARG(!dx_add || ld_add % 4 == 0, "gcd_layernorm_bwd_det: ld_add");
+  CHECK_ARG(x && dy && gamma && dx && dgamma && dbeta, "gcd_layernorm_bwd_det: null pointer");
+  CHECK_ARG(C > 0 && C % 4 == 0 && C <= 1280 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && M > 0,
+            "gcd_layernorm_bwd_det: C=%d (multiple of 4, <= 1280), leading dimensions multiples of 4", C);
+  CHECK_SCRATCH("gcd_layernorm_bwd_det", gcd_layernorm_bwd_det_scratch_floats(M, C));
   const int blocks = ln_blocks(M);
   hipLaunchKernelGGL(ln_bwd_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, dy, lddy, M, C,
                      gamma, eps, dx, lddx, scratch, dx_add, ld_add);
-  D_CHECK_LAUNCH("gcd_layernorm_bwd_det");
+  CHECK_LAUNCH("gcd_layernorm_bwd_det");
   hipLaunchKernelGGL(ln_fold_kernel, dim3((unsigned)((2 * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scratch, blocks,
                      C, dgamma, dbeta);
-  D_CHECK_LAUNCH("gcd_layernorm_bwd_det (fold)");
+  CHECK_LAUNCH("gcd_layernorm_bwd_det (fold)");
   return 0;
 }
 
@@ -562,17 +546,17 @@ extern "C" int64_t gcd_cast_colsum_det_scratch_floats(int64_t M, int C, int64_t 
 extern "C" int gcd_cast_colsum_det_f32(const float* x, int64_t ldx, void* y16, int64_t ldy, int64_t M, int C,
                                        int64_t rows_per_block, float* sums, int to_bf16, float* total, float* scratch,
                                        int64_t scratch_floats, void* stream) {
-  D_CHECK_ARG(x && y16 && sums && M > 0 && C > 0 && C % 8 == 0 && ldx % 4 == 0 && ldy % 8 == 0 &&
-                  (((uintptr_t)x | (uintptr_t)y16) & 15) == 0,
-              "gcd_cast_colsum_det_f32: bad args (C=%d must be a multiple of 8, ldx of 4, ldy of 8, 16-byte aligned rows)", C);
-  D_CHECK_ARG(rows_per_block > 0 && M % rows_per_block == 0, "gcd_cast_colsum_det_f32: M=%lld rows_per_block=%lld",
-              (long long)M, (long long)rows_per_block);
+  CHECK_ARG(x && y16 && sums && M > 0 && C > 0 && C % 8 == 0 && ldx % 4 == 0 && ldy % 8 == 0 &&
+                (((uintptr_t)x | (uintptr_t)y16) & 15) == 0,
+            "gcd_cast_colsum_det_f32: bad args (C=%d must be a multiple of 8, ldx of 4, ldy of 8, 16-byte aligned rows)", C);
+  CHECK_ARG(rows_per_block > 0 && M % rows_per_block == 0, "gcd_cast_colsum_det_f32: M=%lld rows_per_block=%lld",
+            (long long)M, (long long)rows_per_block);
   const int64_t nblk = M / rows_per_block;
   const int colb = (C + 63) / 64;
   int rpc = 0;
   const int64_t chunks = cast_chunks(nblk, colb, rows_per_block, &rpc);
-  D_CHECK_ARG(nblk * chunks <= 65535, "gcd_cast_colsum_det_f32: too many row blocks (%lld)", (long long)(nblk * chunks));
-  D_CHECK_SCRATCH("gcd_cast_colsum_det", nblk * chunks * C);
+  CHECK_ARG(nblk * chunks <= 65535, "gcd_cast_colsum_det_f32: too many row blocks (%lld)", (long long)(nblk * chunks));
+  CHECK_SCRATCH("gcd_cast_colsum_det", nblk * chunks * C);
   const dim3 grid(colb, (unsigned)(nblk * chunks));
   if (to_bf16)
     hipLaunchKernelGGL(cast_colsum_partial_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx,
@@ -580,10 +564,10 @@ extern "C" int gcd_cast_colsum_det_f32(const float* x, int64_t ldx, void* y16, i
   else
     hipLaunchKernelGGL(cast_colsum_partial_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx,
                        (unsigned short*)y16, ldy, rows_per_block, (int)chunks, rpc, C, scratch);
-  D_CHECK_LAUNCH("gcd_cast_colsum_det_f32");
+  CHECK_LAUNCH("gcd_cast_colsum_det_f32");
   hipLaunchKernelGGL(cast_colsum_fold_kernel, dim3((C + 255) / 256, total ? 1u : (unsigned)nblk), dim3(256), 0,
                      (hipStream_t)stream, scratch, (int)nblk, (int)chunks, C, sums, total);
-  D_CHECK_LAUNCH("gcd_cast_colsum_det_f32 (fold)");
+  CHECK_LAUNCH("gcd_cast_colsum_det_f32 (fold)");
   return 0;
 }
 
@@ -597,23 +581,23 @@ extern "C" int gcd_blend_bwd_det_f32(const float* dy, int64_t ld_dy, const float
                                      int64_t ld_t, const float* alpha, int64_t M, int C, int64_t rows_per_frame, float* d_xs,
                                      int64_t ld_dxs, int accumulate_xs, float* d_xt, int64_t ld_dxt, float* d_alpha,
                                      float* scratch, int64_t scratch_floats, void* stream) {
-  D_CHECK_ARG(dy && alpha && d_xt && (!d_alpha || (xs && xt)), "gcd_blend_bwd_det_f32: null pointer");      // (d_xs optional)
-  D_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0 && rows_per_frame > 0 && M % rows_per_frame == 0 && ld_dy % 4 == 0 &&
-                  ld_dxs % 4 == 0 && ld_dxt % 4 == 0 && (!d_alpha || (ld_s % 4 == 0 && ld_t % 4 == 0)),
-              "gcd_blend_bwd_det_f32: M=%lld C=%d rows=%lld, leading dimensions multiples of 4", (long long)M, C,
-              (long long)rows_per_frame);
+  CHECK_ARG(dy && alpha && d_xt && (!d_alpha || (xs && xt)), "gcd_blend_bwd_det_f32: null pointer");      // (d_xs optional)
+  CHECK_ARG(M > 0 && C > 0 && C % 4 == 0 && rows_per_frame > 0 && M % rows_per_frame == 0 && ld_dy % 4 == 0 &&
+                ld_dxs % 4 == 0 && ld_dxt % 4 == 0 && (!d_alpha || (ld_s % 4 == 0 && ld_t % 4 == 0)),
+            "gcd_blend_bwd_det_f32: M=%lld C=%d rows=%lld, leading dimensions multiples of 4", (long long)M, C,
+            (long long)rows_per_frame);
   const int64_t frames = M / rows_per_frame;
-  D_CHECK_ARG(frames < 65536, "gcd_blend_bwd_det_f32: %lld frames", (long long)frames);
+  CHECK_ARG(frames < 65536, "gcd_blend_bwd_det_f32: %lld frames", (long long)frames);
   const int64_t chunks = blend_chunks(frames, rows_per_frame, C);
-  if (d_alpha) D_CHECK_SCRATCH("gcd_blend_bwd_det", frames * chunks);
+  if (d_alpha) CHECK_SCRATCH("gcd_blend_bwd_det", frames * chunks);
   hipLaunchKernelGGL(blend_bwd_partial_kernel, dim3((unsigned)chunks, (unsigned)frames), dim3(256), 0, (hipStream_t)stream, dy,
                      ld_dy, xs, ld_s, xt, ld_t, alpha, C / 4, rows_per_frame, d_xs, ld_dxs, accumulate_xs, d_xt, ld_dxt,
                      d_alpha ? 1 : 0, scratch);
-  D_CHECK_LAUNCH("gcd_blend_bwd_det_f32");
+  CHECK_LAUNCH("gcd_blend_bwd_det_f32");
   if (d_alpha) {
     hipLaunchKernelGGL(blend_fold_kernel, dim3((unsigned)((frames + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scratch,
                        (int)chunks, (int)frames, d_alpha);
-    D_CHECK_LAUNCH("gcd_blend_bwd_det_f32 (fold)");
+    CHECK_LAUNCH("gcd_blend_bwd_det_f32 (fold)");
   }
   return 0;
 }
@@ -624,13 +608,13 @@ extern "C" int64_t gcd_smallm_dgrad_det_scratch_floats(int total_blocks) {
 
 extern "C" int gcd_smallm_dgrad_det(const gcd_smallm_problem* table_dev, int n_prob, int total_blocks, float* scratch,
                                     int64_t scratch_floats, void* stream) {
-  D_CHECK_ARG(table_dev && n_prob > 0 && total_blocks > 0, "gcd_smallm_dgrad_det: empty table");
-  D_CHECK_SCRATCH("gcd_smallm_dgrad_det", gcd_smallm_dgrad_det_scratch_floats(total_blocks));
+  CHECK_ARG(table_dev && n_prob > 0 && total_blocks > 0, "gcd_smallm_dgrad_det: empty table");
+  CHECK_SCRATCH("gcd_smallm_dgrad_det", gcd_smallm_dgrad_det_scratch_floats(total_blocks));
   hipLaunchKernelGGL(smallm_dgrad_partial_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, table_dev,
                      n_prob, scratch);
-  D_CHECK_LAUNCH("gcd_smallm_dgrad_det");
+  CHECK_LAUNCH("gcd_smallm_dgrad_det");
   hipLaunchKernelGGL(smallm_dgrad_fold_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, table_dev,
                      n_prob, (const float*)scratch);
-  D_CHECK_LAUNCH("gcd_smallm_dgrad_det (fold)");
+  CHECK_LAUNCH("gcd_smallm_dgrad_det (fold)");
   return 0;
 }

@@ -15,28 +15,10 @@
 #include <stdio.h>
 
 #include "../../include/gcd_amd_train.h"
+#include "train_common.h"
 
 typedef _Float16 f16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-extern "C" const char* gcd_train_last_error(void);
-void gcd_train_set_error(const char* fmt, ...);
-
-#define T_CHECK_ARG(cond, ...)          \
-  do {                                  \
-    if (!(cond)) {                      \
-      gcd_train_set_error(__VA_ARGS__); \
-      return 2;                         \
-    }                                   \
-  } while (0)
-#define T_CHECK_LAUNCH(what)                                                        \
-  do {                                                                              \
-    hipError_t e_ = hipGetLastError();                                              \
-    if (e_ != hipSuccess) {                                                         \
-      gcd_train_set_error("%s: launch failed: %s", what, hipGetErrorString(e_));    \
-      return 1;                                                                     \
-    }                                                                               \
-  } while (0)
 
 namespace {
 
@@ -387,52 +369,52 @@ __global__ __launch_bounds__(256) void smallm_wgrad_kernel(const gcd_smallm_prob
 
 extern "C" int gcd_train_pack_weights(const gcd_pack_entry* table_dev, int n_entries, int total_tiles, int bf16,
                                       void* stream) {
-  T_CHECK_ARG(table_dev && n_entries > 0 && total_tiles > 0, "gcd_train_pack_weights: empty table");
+  CHECK_ARG(table_dev && n_entries > 0 && total_tiles > 0, "gcd_train_pack_weights: empty table");
   hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, table_dev,
                      n_entries, bf16);
-  T_CHECK_LAUNCH("gcd_train_pack_weights");
+  CHECK_LAUNCH("gcd_train_pack_weights");
   return 0;
 }
 
 extern "C" int gcd_blend_fwd_f32(const float* xs, int64_t ld_s, const float* xt, int64_t ld_t, const float* alpha, int64_t M,
                                  int C, int64_t rows_per_frame, float* y, int64_t ld_y, void* stream) {
-  T_CHECK_ARG(xs && xt && alpha && y, "gcd_blend_fwd_f32: null pointer");
-  T_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0 && rows_per_frame > 0 && M % rows_per_frame == 0 && ld_s % 4 == 0 &&
-                  ld_t % 4 == 0 && ld_y % 4 == 0,
-              "gcd_blend_fwd_f32: M=%lld C=%d rows=%lld", (long long)M, C, (long long)rows_per_frame);
+  CHECK_ARG(xs && xt && alpha && y, "gcd_blend_fwd_f32: null pointer");
+  CHECK_ARG(M > 0 && C > 0 && C % 4 == 0 && rows_per_frame > 0 && M % rows_per_frame == 0 && ld_s % 4 == 0 &&
+                ld_t % 4 == 0 && ld_y % 4 == 0,
+            "gcd_blend_fwd_f32: M=%lld C=%d rows=%lld", (long long)M, C, (long long)rows_per_frame);
   int64_t blocks = (M * (C / 4) + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(blend_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xs, ld_s, xt, ld_t, alpha,
                      M, C / 4, rows_per_frame, y, ld_y);
-  T_CHECK_LAUNCH("gcd_blend_fwd_f32");
+  CHECK_LAUNCH("gcd_blend_fwd_f32");
   return 0;
 }
 
 extern "C" int gcd_blend_bwd_f32(const float* dy, int64_t ld_dy, const float* xs, int64_t ld_s, const float* xt, int64_t ld_t,
                                  const float* alpha, int64_t M, int C, int64_t rows_per_frame, float* d_xs, int64_t ld_dxs,
                                  int accumulate_xs, float* d_xt, int64_t ld_dxt, float* d_alpha_zeroed, void* stream) {
-  T_CHECK_ARG(dy && alpha && d_xt && (!d_alpha_zeroed || (xs && xt)), "gcd_blend_bwd_f32: null pointer");   // (d_xs optional)
-  T_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0 && rows_per_frame > 0 && M % rows_per_frame == 0 && ld_dy % 4 == 0 &&
-                  ld_dxs % 4 == 0 && ld_dxt % 4 == 0 && (!d_alpha_zeroed || (ld_s % 4 == 0 && ld_t % 4 == 0)),
-              "gcd_blend_bwd_f32: M=%lld C=%d rows=%lld", (long long)M, C, (long long)rows_per_frame);
+  CHECK_ARG(dy && alpha && d_xt && (!d_alpha_zeroed || (xs && xt)), "gcd_blend_bwd_f32: null pointer");   // (d_xs optional)
+  CHECK_ARG(M > 0 && C > 0 && C % 4 == 0 && rows_per_frame > 0 && M % rows_per_frame == 0 && ld_dy % 4 == 0 &&
+                ld_dxs % 4 == 0 && ld_dxt % 4 == 0 && (!d_alpha_zeroed || (ld_s % 4 == 0 && ld_t % 4 == 0)),
+            "gcd_blend_bwd_f32: M=%lld C=%d rows=%lld", (long long)M, C, (long long)rows_per_frame);
   const int64_t frames = M / rows_per_frame;
-  T_CHECK_ARG(frames < 65536, "gcd_blend_bwd_f32: %lld frames", (long long)frames);
+  CHECK_ARG(frames < 65536, "gcd_blend_bwd_f32: %lld frames", (long long)frames);
   int64_t chunks = (rows_per_frame * (C / 4) + 255) / 256;
   const int64_t cap = frames >= 512 ? 1 : (4096 + frames - 1) / frames;
   if (chunks > cap) chunks = cap;
   hipLaunchKernelGGL(blend_bwd_kernel, dim3((unsigned)chunks, (unsigned)frames), dim3(256), 0, (hipStream_t)stream, dy, ld_dy,
                      xs, ld_s, xt, ld_t, alpha, C / 4, rows_per_frame, d_xs, ld_dxs, accumulate_xs, d_xt, ld_dxt,
                      d_alpha_zeroed);
-  T_CHECK_LAUNCH("gcd_blend_bwd_f32");
+  CHECK_LAUNCH("gcd_blend_bwd_f32");
   return 0;
 }
 
 extern "C" int gcd_gn_affine_grads(const double* AB, int ninst, int C, float* dgamma, float* dbeta, int accumulate,
                                    void* stream) {
-  T_CHECK_ARG(AB && dgamma && dbeta && ninst > 0 && C > 0, "gcd_gn_affine_grads: bad arguments");
+  CHECK_ARG(AB && dgamma && dbeta && ninst > 0 && C > 0, "gcd_gn_affine_grads: bad arguments");
   hipLaunchKernelGGL(gn_affine_grads_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, AB, ninst, C,
                      dgamma, dbeta, accumulate);
-  T_CHECK_LAUNCH("gcd_gn_affine_grads");
+  CHECK_LAUNCH("gcd_gn_affine_grads");
   return 0;
 }
 
@@ -443,7 +425,7 @@ static int smallm_launch(const char* what, void (*fn)(const gcd_smallm_problem*,
     return 2;
   }
   hipLaunchKernelGGL(fn, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, tab, n_prob);
-  T_CHECK_LAUNCH(what);
+  CHECK_LAUNCH(what);
   return 0;
 }
 

@@ -18,26 +18,9 @@
 #include <stdint.h>
 
 #include "../../include/gcd_amd_train_optim.h"
+#include "train_common.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-void gcd_train_set_error(const char* fmt, ...);      // train_wgrad.hip
-
-#define O_CHECK_ARG(cond, ...)          \
-  do {                                  \
-    if (!(cond)) {                      \
-      gcd_train_set_error(__VA_ARGS__); \
-      return 2;                         \
-    }                                   \
-  } while (0)
-#define O_CHECK_LAUNCH(what)                                                     \
-  do {                                                                           \
-    hipError_t e_ = hipGetLastError();                                           \
-    if (e_ != hipSuccess) {                                                      \
-      gcd_train_set_error("%s: launch failed: %s", what, hipGetErrorString(e_)); \
-      return 1;                                                                  \
-    }                                                                            \
-  } while (0)
 
 namespace {
 
@@ -297,27 +280,27 @@ __global__ __launch_bounds__(256) void apply_kernel(const gcd_optim_tensor* __re
 
 int check_common(const char* what, const void* table, int n_tensors, int64_t total_chunks, const gcd_optim_config* cfg,
                  const void* state) {
-  O_CHECK_ARG(table && cfg && state, "%s: null table, config or state", what);
-  O_CHECK_ARG(((uintptr_t)table & 7) == 0 && ((uintptr_t)state & 15) == 0,
-              "%s: the table must be 8-byte and the state block 16-byte aligned", what);
-  O_CHECK_ARG(n_tensors >= 1, "%s: empty table (n_tensors %d)", what, n_tensors);
-  O_CHECK_ARG(total_chunks >= n_tensors && total_chunks < (1ll << 30),
-              "%s: total_chunks %lld for %d tensors (every tensor has at least one chunk; at most 2^30)", what,
-              (long long)total_chunks, n_tensors);
+  CHECK_ARG(table && cfg && state, "%s: null table, config or state", what);
+  CHECK_ARG(((uintptr_t)table & 7) == 0 && ((uintptr_t)state & 15) == 0,
+            "%s: the table must be 8-byte and the state block 16-byte aligned", what);
+  CHECK_ARG(n_tensors >= 1, "%s: empty table (n_tensors %d)", what, n_tensors);
+  CHECK_ARG(total_chunks >= n_tensors && total_chunks < (1ll << 30),
+            "%s: total_chunks %lld for %d tensors (every tensor has at least one chunk; at most 2^30)", what,
+            (long long)total_chunks, n_tensors);
   return 0;
 }
 
 int check_config(const char* what, const gcd_optim_config* c) {
-  O_CHECK_ARG(c->beta1 >= 0.0 && c->beta1 < 1.0 && c->beta2 >= 0.0 && c->beta2 < 1.0,
-              "%s: betas (%g, %g) must lie in [0, 1)", what, c->beta1, c->beta2);
-  O_CHECK_ARG(c->eps >= 0.0 && c->weight_decay >= 0.0, "%s: eps %g and weight_decay %g must not be negative", what, c->eps,
-              c->weight_decay);
-  O_CHECK_ARG(isfinite(c->grad_scale) && c->grad_scale != 0.f, "%s: grad_scale must be finite and non-zero", what);
-  O_CHECK_ARG(!c->dynamic_scale || (c->growth_factor > 1.f && c->backoff_factor > 0.f && c->backoff_factor < 1.f &&
-                                    c->growth_interval >= 1),
-              "%s: dynamic scaling needs growth_factor > 1, 0 < backoff_factor < 1, growth_interval >= 1", what);
-  O_CHECK_ARG(!c->use_ema || (c->ema_decay >= 0.f && c->ema_decay <= 1.f), "%s: ema_decay %g must lie in [0, 1]", what,
-              c->ema_decay);
+  CHECK_ARG(c->beta1 >= 0.0 && c->beta1 < 1.0 && c->beta2 >= 0.0 && c->beta2 < 1.0,
+            "%s: betas (%g, %g) must lie in [0, 1)", what, c->beta1, c->beta2);
+  CHECK_ARG(c->eps >= 0.0 && c->weight_decay >= 0.0, "%s: eps %g and weight_decay %g must not be negative", what, c->eps,
+            c->weight_decay);
+  CHECK_ARG(isfinite(c->grad_scale) && c->grad_scale != 0.f, "%s: grad_scale must be finite and non-zero", what);
+  CHECK_ARG(!c->dynamic_scale || (c->growth_factor > 1.f && c->backoff_factor > 0.f && c->backoff_factor < 1.f &&
+                                  c->growth_interval >= 1),
+            "%s: dynamic scaling needs growth_factor > 1, 0 < backoff_factor < 1, growth_interval >= 1", what);
+  CHECK_ARG(!c->use_ema || (c->ema_decay >= 0.f && c->ema_decay <= 1.f), "%s: ema_decay %g must lie in [0, 1]", what,
+            c->ema_decay);
   return 0;
 }
 
@@ -332,24 +315,24 @@ extern "C" int gcd_optim_gradstat(const gcd_optim_tensor* table_dev, int n_tenso
                                   int64_t scratch_floats, void* stream) {
   if (int rc = check_common("gcd_optim_gradstat", table_dev, n_tensors, total_chunks, cfg, state_dev)) return rc;
   if (int rc = check_config("gcd_optim_gradstat", cfg)) return rc;
-  O_CHECK_ARG(scratch && scratch_floats >= total_chunks && ((uintptr_t)scratch & 15) == 0,
-              "gcd_optim_gradstat: scratch of %lld floats, need %lld (gcd_optim_gradstat_scratch_floats), 16-byte aligned",
-              (long long)scratch_floats, (long long)total_chunks);
+  CHECK_ARG(scratch && scratch_floats >= total_chunks && ((uintptr_t)scratch & 15) == 0,
+            "gcd_optim_gradstat: scratch of %lld floats, need %lld (gcd_optim_gradstat_scratch_floats), 16-byte aligned",
+            (long long)scratch_floats, (long long)total_chunks);
   hipLaunchKernelGGL(gradstat_partial_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_dev,
                      n_tensors, cfg->grad_scale, scratch);
-  O_CHECK_LAUNCH("gcd_optim_gradstat");
+  CHECK_LAUNCH("gcd_optim_gradstat");
   hipLaunchKernelGGL(gradstat_fold_kernel, dim3(1), dim3(FOLD_THREADS), 0, (hipStream_t)stream, (const float*)scratch,
                      total_chunks, state_dev, *cfg);
-  O_CHECK_LAUNCH("gcd_optim_gradstat (fold)");
+  CHECK_LAUNCH("gcd_optim_gradstat (fold)");
   return 0;
 }
 
 extern "C" int gcd_optim_advance(const gcd_optim_config* cfg, gcd_optim_state* state_dev, void* stream) {
-  O_CHECK_ARG(cfg && state_dev && ((uintptr_t)state_dev & 15) == 0,
-              "gcd_optim_advance: null config or state, or a state block that is not 16-byte aligned");
+  CHECK_ARG(cfg && state_dev && ((uintptr_t)state_dev & 15) == 0,
+            "gcd_optim_advance: null config or state, or a state block that is not 16-byte aligned");
   if (int rc = check_config("gcd_optim_advance", cfg)) return rc;
   hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state_dev, *cfg, 1, cfg->use_ema);
-  O_CHECK_LAUNCH("gcd_optim_advance");
+  CHECK_LAUNCH("gcd_optim_advance");
   return 0;
 }
 
@@ -372,19 +355,19 @@ extern "C" int gcd_optim_apply(const gcd_optim_tensor* table_dev, int n_tensors,
   if (int rc = check_config("gcd_optim_apply", cfg)) return rc;
   hipLaunchKernelGGL(apply_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, n_tensors,
                      (const gcd_optim_state*)state_dev, apply_args(cfg), 1);
-  O_CHECK_LAUNCH("gcd_optim_apply");
+  CHECK_LAUNCH("gcd_optim_apply");
   return 0;
 }
 
 extern "C" int gcd_ema_update(const gcd_optim_tensor* table_dev, int n_tensors, int64_t total_chunks,
                               const gcd_optim_config* cfg, gcd_optim_state* state_dev, void* stream) {
   if (int rc = check_common("gcd_ema_update", table_dev, n_tensors, total_chunks, cfg, state_dev)) return rc;
-  O_CHECK_ARG(cfg->use_ema && cfg->ema_decay >= 0.f && cfg->ema_decay <= 1.f,
-              "gcd_ema_update: use_ema must be set and ema_decay %g must lie in [0, 1]", cfg->ema_decay);
+  CHECK_ARG(cfg->use_ema && cfg->ema_decay >= 0.f && cfg->ema_decay <= 1.f,
+            "gcd_ema_update: use_ema must be set and ema_decay %g must lie in [0, 1]", cfg->ema_decay);
   hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state_dev, *cfg, 0, 1);
-  O_CHECK_LAUNCH("gcd_ema_update (advance)");
+  CHECK_LAUNCH("gcd_ema_update (advance)");
   hipLaunchKernelGGL(apply_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, n_tensors,
                      (const gcd_optim_state*)state_dev, apply_args(cfg), 0);
-  O_CHECK_LAUNCH("gcd_ema_update");
+  CHECK_LAUNCH("gcd_ema_update");
   return 0;
 }

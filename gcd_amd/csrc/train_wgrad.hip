@@ -27,26 +27,18 @@
 #include <stdlib.h>
 
 #include "../../include/gcd_amd_train.h"
+#include "train_common.h"
 #include "train_wgrad_kernel.h"
 
 static thread_local char g_err[512] = "";
-void gcd_train_set_error(const char* fmt, ...) {     // shared with train_ops.hip
+void gcd_train_set_error(const char* fmt, ...) {     // train_common.h
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
 }
-#define set_error gcd_train_set_error
 extern "C" const char* gcd_train_last_error(void) { return g_err; }
 extern "C" int gcd_train_abi_version(void) { return GCD_AMD_TRAIN_ABI_VERSION; }
-
-#define CHECK_ARG(cond, ...)  \
-  do {                        \
-    if (!(cond)) {            \
-      set_error(__VA_ARGS__); \
-      return 2;               \
-    }                         \
-  } while (0)
 
 // Tokens per step of the kernel.  32 is the form A/B'd inside the whole fine-tune step (profiles/r04w_wgrad_ab.txt); the
 // 64-token form (one barrier per 32 MFMAs of a wave, 70 KB of LDS) is 9-25 % faster on the large weight gradients of the
@@ -103,7 +95,7 @@ extern "C" int gcd_wgrad_tr_f16_ex(const void* dy16, int64_t lddy, const void* x
     e = bf16 ? gcd_wgrad::launch<true, 32>(dy16, lddy, x16, ldx, M, N, K, dW, lddw, lay, scratch, s)
              : gcd_wgrad::launch<false, 32>(dy16, lddy, x16, ldx, M, N, K, dW, lddw, lay, scratch, s);
   if (e != hipSuccess) {
-    set_error("gcd_wgrad_tr_f16: launch failed: %s", hipGetErrorString(e));
+    gcd_train_set_error("gcd_wgrad_tr_f16: launch failed: %s", hipGetErrorString(e));
     return 1;
   }
   return 0;
@@ -143,7 +135,7 @@ extern "C" int gcd_wgrad_conv_tr_f16(const void* dy16, int64_t lddy, const void*
   else e = big ? (bf16 ? GCD_WC(true, 64, 2) : GCD_WC(false, 64, 2)) : (bf16 ? GCD_WC(true, 32, 2) : GCD_WC(false, 32, 2));
 #undef GCD_WC
   if (e != hipSuccess) {
-    set_error("gcd_wgrad_conv_tr_f16: launch failed: %s", hipGetErrorString(e));
+    gcd_train_set_error("gcd_wgrad_conv_tr_f16: launch failed: %s", hipGetErrorString(e));
     return 1;
   }
   return 0;

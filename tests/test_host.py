@@ -16,77 +16,15 @@ GOLD = ROOT / "tests" / "golden"
 
 
 # ------------------------------------------------------------------------------------ C ABI surface
-def test_library_exports_every_declared_symbol():
-    from gcd_amd import _lib
-    header = (ROOT / "include" / "gcd_amd.h").read_text()
-    declared = set(re.findall(r"^\s*(?:int|int64_t|const char\*)\s+(gcd_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
-    lib = _lib.load()                       # raises if the .so has not been built
-    for name in declared:
-        assert hasattr(lib, name), name
-    assert lib.gcd_abi_version() == _lib.ABI_VERSION == 9
-
-
 def test_train_library_exports_every_declared_symbol():
-    """libgcd_amd_train.so (the fine-tune step's own kernels) against include/gcd_amd_train.h; argument validation is
-    observable without a GPU."""
+    """libgcd_amd_train.so (the fine-tune step's own kernels; its symbols: tests/test_libraries_host.py): the scratch size
+    of the weight gradient, and argument validation, which is observable without a GPU."""
     from gcd_amd import _lib
-    header = (ROOT / "include" / "gcd_amd_train.h").read_text()
-    declared = set(re.findall(r"^\s*(?:int|int64_t|const char\*)\s+(gcd_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.TRAIN_SIGNATURES), (declared ^ set(_lib.TRAIN_SIGNATURES))
     lib = _lib.load_train()
-    assert lib.gcd_train_abi_version() == _lib.TRAIN_ABI_VERSION
     assert lib.gcd_wgrad_tr_scratch_floats(43008, 320, 1280) == 64 * 320 * 1280      # 2 x 8 tiles of 160 -> 64 token slices
     assert lib.gcd_wgrad_tr_scratch_floats(10752, 640, 640) == 40 * 640 * 640        # 5 x 5 tiles of 128 -> 40 token slices
     assert lib.gcd_wgrad_tr_f16(16, 320, 16, 1280, 100, 321, 1280, 0, 16, 1280, 16, 1 << 30, None) != 0
     assert b"multiples of 8" in lib.gcd_train_last_error()
-
-
-def test_gemm_desc_layout_matches_header(tmp_path):
-    """ctypes mirror of gcd_gemm_desc has the C struct's offsets and size (checked with gcc)."""
-    import shutil
-    import subprocess
-    from gcd_amd import _lib
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not available")
-    fields = [f[0] for f in _lib.GemmDesc._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT / "include" / "gcd_amd.h"}"',
-           'int main(void) {']
-    src += [f'  printf("{n} %zu\\n", offsetof(gcd_gemm_desc, {n}));' for n in fields]
-    src += ['  printf("sizeof %zu\\n", sizeof(gcd_gemm_desc));', '  return 0;', '}']
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c11", "-o", str(exe), str(c)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    for n in fields:
-        assert int(out[n]) == getattr(_lib.GemmDesc, n).offset, n
-    assert int(out["sizeof"]) == ctypes.sizeof(_lib.GemmDesc)
-
-
-@pytest.mark.parametrize("cname,pyname", [("gcd_pack_entry", "PackEntry"), ("gcd_smallm_problem", "SmallmProblem")])
-def test_train_table_structs_match_header(tmp_path, cname, pyname):
-    """ctypes mirrors of the device-table structs of include/gcd_amd_train.h (the multi-tensor weight pack, the grouped
-    few-row Linears) have the C structs' offsets and sizes (checked with gcc)."""
-    import shutil
-    import subprocess
-    from gcd_amd import _lib
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not available")
-    cls = getattr(_lib, pyname)
-    fields = [f[0] for f in cls._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT / "include" / "gcd_amd_train.h"}"',
-           'int main(void) {']
-    src += [f'  printf("{n} %zu\\n", offsetof({cname}, {n}));' for n in fields]
-    src += [f'  printf("sizeof %zu\\n", sizeof({cname}));', '  return 0;', '}']
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c11", "-o", str(exe), str(c)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    for n in fields:
-        assert int(out[n]) == getattr(cls, n).offset, n
-    assert int(out["sizeof"]) == ctypes.sizeof(cls)
 
 
 def test_ops_refuse_cpu_tensors_and_bad_args():

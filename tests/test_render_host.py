@@ -1,15 +1,12 @@
 """CPU: the C ABI of libgcd_amd_render.so (include/gcd_amd_render.h) — header, binding table and exported symbols are one
-set; the library builds from a tree that holds no build product, through build(); every entry validates its arguments
+set and the library builds from a tree that holds no build product (tests/test_libraries_host.py); every entry validates its arguments
 before any launch; the scratch sizes are what the header says; the host module refuses what is not a GPU tensor; and the
 accumulation scheme of the splat (four reference exponents per pixel, l for the denominator and l + ln c per channel, integer maxima, fixed-point integer sums), restated
 here with integer tensors, reproduces the reference's images of tests/golden/render_tiny.pt at the bars of DESIGN.md §12.2.
 The last one keeps the scheme itself pinned where no GPU is present."""
 import ctypes as C
-import importlib.util
 import math
 import re
-import shutil
-import struct
 from pathlib import Path
 
 import pytest
@@ -21,39 +18,13 @@ ROOT = Path(__file__).resolve().parent.parent
 DECL = r"^\s*(?:int|int64_t|const char\*)\s+(gcd_\w+)\s*\("
 
 
-def _dynamic_exports(path: Path):
-    """Names of the defined global functions in the .dynsym of an ELF64 little-endian shared object."""
-    d = path.read_bytes()
-    assert d[:6] == b"\x7fELF\x02\x01", "an ELF64 little-endian file"
-    shoff, = struct.unpack_from("<Q", d, 0x28)
-    shentsize, shnum = struct.unpack_from("<HH", d, 0x3A)
-    sections = [struct.unpack_from("<IIQQQQIIQQ", d, shoff + i * shentsize) for i in range(shnum)]
-    names = set()
-    for (_, sh_type, _, _, off, size, link, _, _, entsize) in sections:
-        if sh_type != 11:                      # SHT_DYNSYM
-            continue
-        stroff = sections[link][4]
-        for j in range(size // entsize):
-            st_name, st_info, _, st_shndx, _, _ = struct.unpack_from("<IBBHQQ", d, off + j * entsize)
-            if st_shndx != 0 and (st_info & 0xF) == 2 and (st_info >> 4) == 1:      # defined, FUNC, GLOBAL
-                names.add(d[stroff + st_name:d.index(b"\0", stroff + st_name)].decode())
-    return names
-
-
 def test_render_header_binding_table_and_exports_are_one_set():
     from gcd_amd import _lib
     from gcd_amd.csrc import build as b
-    b.build(verbose=False)                     # a no-op when the libraries are current
     header = (ROOT / "include" / "gcd_amd_render.h").read_text()
-    declared = set(re.findall(DECL, header, flags=re.M))
-    assert declared == set(_lib.RENDER_SIGNATURES), declared ^ set(_lib.RENDER_SIGNATURES)
-    exported = {n for n in _dynamic_exports(_lib.RENDER_LIB_PATH) if n.startswith("gcd_")}
-    assert exported == declared, exported ^ declared
+    declared = set(re.findall(DECL, header, flags=re.M))      # == table == exports: tests/test_libraries_host.py
     assert {"gcd_render_abi_version", "gcd_render_last_error", "gcd_render_scratch_bytes", "gcd_render_splat",
             "gcd_render_fill_resize_f32"} <= declared
-    lib = _lib.load_render()
-    assert lib.gcd_render_abi_version() == _lib.RENDER_ABI_VERSION == 1
-    assert int(re.search(r"#define GCD_AMD_RENDER_ABI_VERSION (\d+)", header).group(1)) == 1
     for name in ("F16", "F32", "F64", "U8", "MAX_CAMERAS", "CAM_DOUBLES", "MAX_KERNEL"):
         assert int(re.search(rf"#define GCD_RENDER_{name} (\d+)", header).group(1)) == getattr(_lib, "RENDER_" + name), name
     # the descriptor of the binding has the header's fields, in the header's order
@@ -62,40 +33,9 @@ def test_render_header_binding_table_and_exports_are_one_set():
     fields = [n.strip(" *") for decl in body.split(";") if decl.strip() for n in decl.strip().split(None, 1)[1].replace(
         "void*", "").replace("double*", "").replace("float*", "").replace("int64_t*", "").split(",")]
     assert fields == [f[0] for f in _lib.RenderSplatDesc._fields_], fields
-    # a library of its own: the main header, its table, its ABI version and the step's source digest do not know it
-    main_header = (ROOT / "include" / "gcd_amd.h").read_text()
-    assert "gcd_render" not in main_header and not (declared & set(_lib.SIGNATURES)) and _lib.ABI_VERSION == 9
-    assert set(re.findall(DECL, main_header, flags=re.M)) == set(_lib.SIGNATURES)
-    assert not (set(b.RENDER_SOURCES) & set(b.SOURCES + b.TRAIN_SOURCES + b.SAMPLER_SOURCES + b.METRICS_SOURCES))
-    assert not (set(b.RENDER_HEADERS) & set(b.HEADERS + b.TRAIN_HEADERS + b.SAMPLER_HEADERS + b.METRICS_HEADERS))
-
-
-def test_render_library_builds_from_a_clean_tree_through_build(tmp_path):
-    """A copy of the build script, the source and the header, and nothing built: build() makes the library even when
-    the main library is current (it returns early then), and a second call compiles nothing."""
-    (tmp_path / "gcd_amd" / "csrc").mkdir(parents=True)
-    (tmp_path / "include").mkdir()
-    for rel in ("gcd_amd/csrc/build.py", "gcd_amd/csrc/render.hip", "include/gcd_amd_render.h"):
-        shutil.copy(ROOT / rel, tmp_path / rel)
-    spec = importlib.util.spec_from_file_location("clean_tree_build_render", tmp_path / "gcd_amd" / "csrc" / "build.py")
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    assert m.LIB_RENDER == tmp_path / "gcd_amd" / "libgcd_amd_render.so" and not m.LIB_RENDER.exists()
-    called = []
-    m.build_train = lambda **k: called.append("train")
-    m.build_sampler = lambda **k: called.append("sampler")
-    m.build_metrics = lambda **k: called.append("metrics")
-    m._digest = lambda: "current"
-    m.LIB.write_bytes(b"")
-    m.STAMP.write_text("current")
-    assert m.build(verbose=False) == m.LIB and called == ["train", "sampler", "metrics"]
-    assert m.LIB_RENDER.exists() and m.STAMP_RENDER.exists()
-    exported = {n for n in _dynamic_exports(m.LIB_RENDER) if n.startswith("gcd_")}
-    assert "gcd_render_splat" in exported and "gcd_render_fill_resize_f32" in exported
-    before = m.LIB_RENDER.stat().st_mtime_ns
-    m.build(verbose=False)
-    assert m.LIB_RENDER.stat().st_mtime_ns == before
-    assert ".libgcd_amd_render.stamp" in (ROOT / ".gitignore").read_text().split()
+    # a library of its own (its symbols, sources and headers are apart from the others': tests/test_libraries_host.py)
+    assert "gcd_render" not in (ROOT / "include" / "gcd_amd.h").read_text()
+    assert b.LIBRARIES["gcd_amd_render"].sources == ["render.hip"] and "render.hip" not in b.SOURCES
 
 
 def test_render_entries_validate_their_arguments_before_any_launch():
