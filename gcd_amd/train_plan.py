@@ -455,6 +455,11 @@ class TrainPlan:
         dx = plan.backward(d_out)                                 # parameter .grad filled; returns d x | None
         optimizer.step(); plan.repack()                           # after the parameters changed
 
+    `forward(..., need_inputs=(x, context, y))` asks for input gradients as well (`unet_forward_planned(input_grads=True)`:
+    a conditioner trained through `vector` / `crossattn`): `backward` leaves them in `plan.input_grads`, fresh tensors in the
+    inputs' shapes.  d y and d context come out of the stage-1 few-row problems, which then carry a `dx`; d x is the first
+    convolution's dgrad.
+
     Parameter gradients live in ONE flat fp32 buffer (`p.grad` are views of it): weight gradients are written in place by
     the kernels, the 1-D parameters' region is zeroed by one memset per step.  `accumulate=True` (gradient accumulation,
     main.py:950) adds onto what is there instead.  `on_param_grad(p)` is called once per parameter as soon as its gradient
@@ -468,6 +473,8 @@ class TrainPlan:
         self.listeners_enabled = True
         self.accumulate = False
         self.need_dx = False
+        self.need_inputs = (False, False, False)
+        self.input_grads = (None, None, None)
         dev = next(unet.parameters()).device
         self.device = dev
         if dev.type != "cuda":
@@ -841,9 +848,11 @@ class TrainPlan:
         return A._colsum(x.contiguous(), rows, sink=self)
 
     # ---- forward ----
-    def forward(self, x, timesteps, context, y, num_video_frames: int, image_only_indicator, record: bool = True):
+    def forward(self, x, timesteps, context, y, num_video_frames: int, image_only_indicator, record: bool = True,
+                need_inputs=(False, False, False)):
         """record=False (validation / image logging under torch.no_grad()): nothing is kept for a backward pass — no unit
-        contexts, no trace.  The plan holds ONE forward's state: a backward of an EARLIER forward raises (see `_serial`)."""
+        contexts, no trace.  The plan holds ONE forward's state: a backward of an EARLIER forward raises (see `_serial`).
+        need_inputs: which of (x, context, y) get a gradient in `backward` (-> `plan.input_grads`)."""
         unet = self.unet
         ops._need_gpu(x, timesteps, context, y)
         # every forward gets a serial number; `_PlannedUNet.backward` refuses to run for any but the LATEST forward (its
@@ -855,6 +864,10 @@ class TrainPlan:
         if context.shape[1] != 1:
             raise NotImplementedError("gcd_amd implements the single-token (CLIP image) context of SVD / GCD")
         self.N, self.T, self.H, self.W = N, T, H, W
+        self.need_inputs = tuple(bool(f) and record for f in need_inputs)
+        self.need_dx = self.need_inputs[0]
+        self.input_grads = (None, None, None)
+        self._in_like = tuple((tuple(t.shape), t.dtype) for t in (x, context, y))
         if not torch.cuda.is_current_stream_capturing():
             self._decide_checkpoint(N * H * W)
         self.ioi = image_only_indicator.to(x.device)
@@ -926,7 +939,25 @@ class TrainPlan:
             del sv, hin
         self._small_backward()
         self.accumulate = False
-        return None
+        self.input_grads = self._collect_input_grads(d)
+        return self.input_grads[0]
+
+    def _collect_input_grads(self, d_first):
+        """(d x, d context, d y) in the inputs' shapes and dtypes, None where not asked for: FRESH tensors (the few-row
+        destinations are views of the step's arena, which the next forward zeroes)."""
+        need_x, need_c, need_y = self.need_inputs
+        N, T, H, W = self.N, self.T, self.H, self.W
+        (xs, xd), (cs, cd), (ys, yd) = self._in_like
+        dx = dc = dy = None
+        if need_x:          # the first convolution's dgrad, token-major [N H W, Cin]
+            dx = d_first.reshape(N, H, W, -1).permute(0, 3, 1, 2).contiguous().to(xd)
+        if need_c:          # every frame's spatial to_v chains + the temporal chains of its clip on the clip's first frame
+            dc = self._d_ctx2d.clone()
+            dc.view(N // T, T, -1)[:, 0] += self._d_ctx_clip
+            dc = dc.reshape(cs).to(cd)
+        if need_y:
+            dy = self._d_yv.clone().reshape(ys).to(yd)
+        return dx, dc, dy
 
     # ---- the few-row side: embeddings, emb_layers, cross-attention vectors, position embeddings ----
     def _small_forward(self, timesteps, context, y):
@@ -946,15 +977,26 @@ class TrainPlan:
         ctx2d.copy_(context.reshape(N, -1))
         yv = new(N, y.shape[1])
         yv.copy_(y)
+        # input gradients (need_inputs): d y = the column slices [:adm] | [adm:] of ONE zeroed buffer (row stride = lddx),
+        # d context = one destination shared by every spatial to_v problem + one, a row per clip, shared by the temporal
+        # ones.  The dgrad kernels store dx element by element (smallm_dgrad_kernel, smallm_dgrad_fold_kernel): a slice needs
+        # a float's alignment only, and `_SmallGroup.add` wants K % 4 == 0 of both slices anyway.  The destinations are taken
+        # from the arena on every step, asked for or not, so that nothing after them moves when the request changes; the
+        # stage-1 table that carries them is cached under its own name, next to the one without.
+        _, need_c, need_y = self.need_inputs
+        self._d_yv = zeros(N, y.shape[1])
+        dyv = (self._d_yv[:, :adm], self._d_yv[:, adm:]) if need_y else (None, None)
+        self._d_ctx2d = zeros(N, ctx2d.shape[1])
+        self._d_ctx_clip = zeros(clips, ctx2d.shape[1])
         # stage 1: first Linear of every embedding MLP (inputs known up front)
-        g1 = _SmallGroup(dev, "g1")
+        g1 = _SmallGroup(dev, "g1" + ("+dc" if need_c else "") + ("+dy" if need_y else ""))
         t_in = temb(timesteps, unet.model_channels, getattr(unet, "max_ddpm_temb_period", 10000.0))
-        mlps = [(unet.time_embed, t_in), (unet.label_emb[0], yv[:, :adm])]
+        mlps = [(unet.time_embed, t_in, None), (unet.label_emb[0], yv[:, :adm], dyv[0])]
         if unet.aux_emb_dim > 0:
-            mlps.append((unet.aux_label_emb, yv[:, adm:]))
+            mlps.append((unet.aux_label_emb, yv[:, adm:], dyv[1]))
         hid = []
-        for seq, xin in mlps:
-            hid.append(g1.add(xin, seq[0], new(N, seq[0].weight.shape[0])))
+        for seq, xin, dxin in mlps:
+            hid.append(g1.add(xin, seq[0], new(N, seq[0].weight.shape[0]), dx=dxin))
         pos_hid = []
         for i, tr in enumerate(self.transformers):
             key = (i, N, T)
@@ -972,8 +1014,10 @@ class TrainPlan:
         for tr in self.transformers:
             row = []
             for sb, tb in zip(tr.transformer_blocks, tr.time_stack):
-                vs = g1.add(ctx2d, sb.attn2.to_v, new(N, sb.attn2.to_v.weight.shape[0]))
-                vt = g1.add(ctx_clip, tb.attn2.to_v, new(clips, tb.attn2.to_v.weight.shape[0]))
+                vs = g1.add(ctx2d, sb.attn2.to_v, new(N, sb.attn2.to_v.weight.shape[0]),
+                            dx=self._d_ctx2d if need_c else None)
+                vt = g1.add(ctx_clip, tb.attn2.to_v, new(clips, tb.attn2.to_v.weight.shape[0]),
+                            dx=self._d_ctx_clip if need_c else None)
                 row.append((vs, vt))
             cav.append(row)
         g1.forward(self)
@@ -981,7 +1025,7 @@ class TrainPlan:
         g2 = _SmallGroup(dev, "g2")
         self._d_hid = [zeros(*h.shape) for h in hid]
         embs = [g2.add(h, seq[2], new(N, E), silu_in=True, dx=self._d_hid[i], dx_silu=True)
-                for i, ((seq, _), h) in enumerate(zip(mlps, hid))]      # (own outputs: problems of a launch run concurrently)
+                for i, ((seq, _, _), h) in enumerate(zip(mlps, hid))]      # (own outputs: problems of a launch run concurrently)
         self._d_pos_hid = [zeros(*h.shape) for h in pos_hid]
         pos = []
         for tr, h, dh in zip(self.transformers, pos_hid, self._d_pos_hid):
@@ -1036,7 +1080,7 @@ class TrainPlan:
             for (d_ca_s, d_ca_t, _) in gr:
                 dys += [d_ca_s.contiguous(), d_ca_t.contiguous()]
         g2.backward(self, dys)
-        # stage 1: first Linears (inputs are data: no dx)
+        # stage 1: first Linears (inputs are data: no dx — but for y and context when `need_inputs` asks)
         dys = list(self._d_hid) + list(self._d_pos_hid)
         for drow in self._d_cav:
             for dvs, dvt in drow:
@@ -1067,7 +1111,8 @@ class GraphedPlan:
     forward pass is captured, and the backward pass at the first backward after it; later steps copy the inputs into the
     static buffers and replay — no Python, no per-launch host work between the kernels.  What stays eager: the loss between
     the two graphs, the optimizer step, gradient accumulation (a backward that must ADD falls back to the eager pass), any
-    call whose signature differs.  The weight pack (`repack`) is part of the forward graph: it re-reads the parameters the
+    call whose signature differs, and any call that asks for input gradients (`need_inputs`: never captured, never None).
+    The weight pack (`repack`) is part of the forward graph: it re-reads the parameters the
     optimizer just changed.  Listeners (GradBucketer) are told about every gradient after the backward graph has been
     enqueued, i.e. the data-parallel exchange is not overlapped in this mode."""
     WARMUP = 2
@@ -1086,8 +1131,13 @@ class GraphedPlan:
         self.static = None
         self.mode = "eager"
 
-    def forward(self, x, timesteps, context, y, T, ioi):
+    def forward(self, x, timesteps, context, y, T, ioi, need_inputs=(False, False, False)):
         plan = self.plan
+        if any(need_inputs):
+            # input gradients are not captured: this call is the eager planned pass, forward and backward; the graphs
+            # (and the warm-up count) of the calls without them stay as they are
+            self.mode = "eager"
+            return plan.forward(x, timesteps, context, y, T, ioi, need_inputs=need_inputs)
         sig = (tuple(x.shape), tuple(timesteps.shape), tuple(context.shape), tuple(y.shape), tuple(ioi.shape), T,
                A.FWD_DTYPE, A.GRAD_DTYPE, plan.checkpoint_policy, x.dtype, context.dtype, y.dtype, A.DETERMINISTIC)
         if sig != self.sig:
@@ -1158,10 +1208,12 @@ class _PlannedUNet(torch.autograd.Function):
     def forward(ctx, plan, anchor, x, timesteps, context, y, T, ioi):
         ctx.plan = plan
         ctx.graphed = USE_GRAPH and plan.graphed is not None
+        # (plan, anchor, x, timesteps, context, y, T, ioi): the inputs autograd wants a gradient for
+        need = (ctx.needs_input_grad[2], ctx.needs_input_grad[4], ctx.needs_input_grad[5])
         if ctx.graphed:
-            out = plan.graphed.forward(x, timesteps, context, y, T, ioi)
+            out = plan.graphed.forward(x, timesteps, context, y, T, ioi, need_inputs=need)
         else:
-            out = plan.forward(x, timesteps, context, y, T, ioi)
+            out = plan.forward(x, timesteps, context, y, T, ioi, need_inputs=need)
         ctx.serial = getattr(plan, "_serial", 0)
         return out
 
@@ -1176,7 +1228,12 @@ class _PlannedUNet(torch.autograd.Function):
             plan.graphed.backward(d_out)
         else:
             plan.backward(d_out, accumulate=plan.grads_are_live())
-        return (None,) * 8
+        dx, dc, dy = plan.input_grads
+        plan.input_grads = (None, None, None)
+        for i, g in ((2, dx), (4, dc), (5, dy)):
+            if ctx.needs_input_grad[i] and g is None:
+                raise RuntimeError("gcd_amd planned training pass: an input gradient was asked for and not computed")
+        return (None, None, dx, None, dc, dy, None, None)
 
 
 # GCD_TRAIN_GRAPH=1: capture the planned forward and backward passes as two hipGraphs after two eager steps (GraphedPlan)
@@ -1187,6 +1244,22 @@ USE_GRAPH = _os.environ.get("GCD_TRAIN_GRAPH", "0") == "1"
 def set_use_graph(on: bool) -> None:
     global USE_GRAPH
     USE_GRAPH = bool(on)
+
+
+# GCD_TRAIN_INPUT_GRADS=1: a call whose x, context or y requires grad (a conditioner trained through `vector` /
+# `crossattn`, as the kubric configs train SphericalEmbedder.proj) stays on the planned pass, which then also computes
+# those gradients.  Off by default: such a call goes to the operator-level autograd engine, as before.
+INPUT_GRADS = _os.environ.get("GCD_TRAIN_INPUT_GRADS", "0") == "1"
+
+
+def set_input_grads(on: bool) -> None:
+    global INPUT_GRADS
+    INPUT_GRADS = bool(on)
+
+
+def input_grads_on(input_grads: Optional[bool] = None) -> bool:
+    """The keyword of `unet_forward_planned` when given, else the module setting (set_input_grads / GCD_TRAIN_INPUT_GRADS)."""
+    return INPUT_GRADS if input_grads is None else bool(input_grads)
 
 
 def plan_for(unet: VideoUNet, use_checkpoint: Optional[bool] = None) -> TrainPlan:
@@ -1206,11 +1279,14 @@ def plan_for(unet: VideoUNet, use_checkpoint: Optional[bool] = None) -> TrainPla
 
 
 def unet_forward_planned(unet: VideoUNet, x, timesteps, context, y, num_video_frames: int, image_only_indicator,
-                         use_checkpoint: Optional[bool] = None) -> torch.Tensor:
-    """Drop-in for `training.unet_forward_train`: same arguments, same result, one autograd node."""
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, context, y)):
-        # The planned pass computes PARAMETER gradients only (its few-row Linears treat their inputs as data).  A
-        # conditioner trained through `vector` / `crossattn` (the kubric configs train SphericalEmbedder.proj,
+                         use_checkpoint: Optional[bool] = None, input_grads: Optional[bool] = None) -> torch.Tensor:
+    """Drop-in for `training.unet_forward_train`: same arguments, same result, one autograd node.  input_grads: None = the
+    module setting (`set_input_grads`, GCD_TRAIN_INPUT_GRADS), True = inputs that require grad get their gradients from the
+    planned pass, False = such a call runs on the operator-level engine."""
+    if torch.is_grad_enabled() and not input_grads_on(input_grads) and \
+            any(t is not None and t.requires_grad for t in (x, context, y)):
+        # Switch off: the planned pass computes PARAMETER gradients only (its few-row Linears treat their inputs as data).
+        # A conditioner trained through `vector` / `crossattn` (the kubric configs train SphericalEmbedder.proj,
         # encoders/modules.py) or a gradient with respect to x needs the operator-level autograd engine: use it, loudly once.
         from . import training as _TR
         if not getattr(unet_forward_planned, "_warned", False):

@@ -271,10 +271,17 @@ class TrainDenoiser(nn.Module):
     training-mode UNet underneath: `denoiser(network, input, sigma, cond, **kwargs)`."""
 
     def __init__(self, scaling_config: Dict, use_checkpoint: Optional[bool] = None, engine: Optional[str] = None,
-                 deterministic: Optional[bool] = None):
+                 deterministic: Optional[bool] = None, input_grads: Optional[bool] = None):
         super().__init__()
         self.scaling = instantiate_from_config(scaling_config)
         self.use_checkpoint = use_checkpoint        # None: follow the network's `use_checkpoint`
+        if input_grads is not None and not isinstance(input_grads, bool):
+            raise ValueError(f"input_grads must be None, True or False, got {input_grads!r}")
+        # planned engine only.  None: the process default (train_plan.set_input_grads / GCD_TRAIN_INPUT_GRADS).  True: a
+        # trainable conditioner (cfg4: SphericalEmbedder through cond["vector"]) gets its gradient from the planned pass —
+        # d vector, d crossattn and d input (autograd splits the latter over the latents and cond["concat"]); False / off:
+        # such a step runs on the operator-level engine
+        self.input_grads = input_grads
         if engine not in (None, "planned", "autograd"):
             raise ValueError(f"train engine must be 'planned' or 'autograd', got {engine!r}")
         self.engine = engine                        # None: the process default (set_train_engine / GCD_TRAIN_ENGINE)
@@ -295,14 +302,15 @@ class TrainDenoiser(nn.Module):
         concat = cond.get("concat")
         if concat is not None and concat.numel() > 0:
             x = torch.cat((x, concat.type_as(x)), dim=1)
+        kw = dict(use_checkpoint=self.use_checkpoint)
         if (self.engine or TRAIN_ENGINE) == "planned":
             from .train_plan import unet_forward_planned as run
+            kw["input_grads"] = self.input_grads
         else:
             run = unet_forward_train
         out = run(unet, x, c_noise.reshape(sigma_shape), cond.get("crossattn"),
                   cond.get("vector"), additional_model_inputs["num_video_frames"],
-                  additional_model_inputs["image_only_indicator"],
-                  use_checkpoint=self.use_checkpoint)
+                  additional_model_inputs["image_only_indicator"], **kw)
         return out * c_out + input * c_skip
 
 
@@ -783,6 +791,12 @@ class GradBucketer:
         self._hooks = []
         self._reset_ready()
         if self.active:
+            # Parameters OUTSIDE the UNet (a trainable conditioner's: SphericalEmbedder.proj behind cond["vector"], trained
+            # through the planned pass's input gradients) are ordinary autograd leaves: torch accumulates their .grad after
+            # `_PlannedUNet.backward` has returned and fires the hook below; no listener call ever names them.  One bucketer
+            # takes both sets: the hook and the listener are the same `_on_grad`.  Wherever such parameters stand in
+            # `params`, their gradients are the last of the pass — name them in `late`, next to
+            # `train_plan.late_parameters(net)` (tests/test_train_inputs_host.py).
             for p in self.params:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad))
             # the planned engine (train_plan.py) writes .grad itself, so torch's hooks never fire for its parameters: it
