@@ -359,7 +359,8 @@ class StandardDiffusionLoss(nn.Module):
         super().__init__()
         assert loss_type in ["l2", "l1", "lpips"]
         if loss_type == "lpips":
-            raise NotImplementedError("loss_type 'lpips' needs the LPIPS network's torchvision weights")
+            raise NotImplementedError("loss_type 'lpips' needs gradients through the LPIPS tower; gcd_amd.lpips.LPIPS is "
+                                      "forward-only (the validation metric)")
         self.harmonize_sigmas = harmonize_sigmas
         self.sigma_sampler = instantiate_from_config(sigma_sampler_config)
         self.loss_weighting = instantiate_from_config(loss_weighting_config)
