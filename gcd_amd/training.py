@@ -12,9 +12,9 @@ all-reduce, `configure_optimizers` (diffusion.py:412-431).  Here:
     wrappers.py:23-34);
   * `StandardDiffusionLoss`: drop-in for the `loss_fn_config.target` socket: EDM sigma sampling
     harmonised per clip, noised input, denoiser call, L2 / L1, the annealed top-k "focal" loss and the
-    EDM weighting.  Elementwise torch on device tensors (the reference's own code is that too); the
-    ParallelDomain class re-weighting needs the RGB ground truth of a dataset that is not part of the
-    path and raises NotImplementedError when requested;
+    EDM weighting, the ParallelDomain class re-weighting.  Elementwise torch on device tensors by default (the
+    reference's own code is that too); `set_loss_engine("hip")` / GCD_TRAIN_LOSS=hip moves `get_loss` and its
+    gradient to the kernels of gcd_amd/loss_device.py (DESIGN.md §11.3);
   * `AdamHIP`: torch.optim.Adam semantics on `gcd_adam_step`;
   * `allreduce_gradients`: the data-parallel exchange (RCCL over xGMI; gloo in the CPU tests): flat
     fp32 buckets, asynchronous all-reduce, averaged in place.
@@ -153,6 +153,19 @@ def set_train_engine(name: str) -> None:
 
 
 set_train_engine(os.environ.get("GCD_TRAIN_ENGINE", "planned"))
+# Which code computes StandardDiffusionLoss.get_loss: "torch" (torch ops and the autograd tape) or "hip" (gcd_amd/loss_device.py:
+# one launch for the class weight map, one for the loss, one for its gradient; GCD_TRAIN_LOSS=hip).
+LOSS_ENGINE = "torch"
+
+
+def set_loss_engine(name: str) -> None:
+    global LOSS_ENGINE
+    if name not in ("torch", "hip"):
+        raise ValueError(f"loss engine must be 'torch' or 'hip', got {name!r}")
+    LOSS_ENGINE = name
+
+
+set_loss_engine(os.environ.get("GCD_TRAIN_LOSS", "torch"))
 # Bit-reproducible steps: the backward pass's five order-dependent fp32 sums run as partial sums + an ordered fold
 # (autograd_ops.set_deterministic; GCD_TRAIN_DETERMINISTIC=1).  Off by default.
 set_deterministic = A.set_deterministic
@@ -395,19 +408,41 @@ class StandardDiffusionLoss(nn.Module):
         w = append_dims(self.loss_weighting(sigmas), input.ndim)
         return self.get_loss(out, input, w, batch)
 
+    def _pd_classes(self) -> list:
+        """[((r, g, b), weight), ...] of the ParallelDomain classes this loss up-weights, in the reference's order."""
+        classes = []
+        if self.pd_person_weight > 1.0:
+            classes += [(rgb, self.pd_person_weight) for rgb in PD_PERSON_RGB.values()]
+        if self.pd_vehicle_weight > 1.0:
+            classes += [(rgb, self.pd_vehicle_weight) for rgb in PD_VEHICLE_RGB.values()]
+        return classes
+
+    def _get_loss_hip(self, model_output, target, w, batch):
+        """get_loss on the device (gcd_amd/loss_device.py).  None: a `focus_top` so small that the reference averages an
+        empty set (keep < 1 inside the annealing) — that stays on the torch path."""
+        from . import loss_device
+        ops._need_gpu(model_output, target, w)
+        n = target[0].numel()
+        progress = min(max(batch["global_step"] / self.focus_steps, 0.0), 1.0) if self.focus_steps > 0 else 0.0
+        cur_top = (1.0 - progress) + self.focus_top * progress
+        keep = int(n * cur_top) if cur_top < 1.0 else 0           # 0: no focal selection
+        if cur_top < 1.0 and keep < 1:
+            return None
+        wmap = None
+        classes = self._pd_classes()
+        if classes:
+            jpg = batch["jpg"].detach().to(device=target.device, dtype=torch.float32).contiguous()
+            wmap = loss_device.class_weight_map(jpg, target.shape[2:4], classes)
+        return loss_device.focal_loss(model_output, target, w, keep, self.loss_type, wmap)
+
     def _pd_class_weight_map(self, gt_rgb: torch.Tensor, latent_hw) -> torch.Tensor:
         """loss.py:196-230 (configs/train_pardom_semantic.yaml:145-146): per latent pixel, sum over the selected
         ParallelDomain classes of (class weight - 1) x the fraction of the pixels of its 8 x 8 square whose
         semantic-map colour matches the class (mean absolute channel difference < 0.02 on the [-1, 1] range).
         Returns (BT, 1, Hl, Wl); the reference adds `loss_raw * mask * (weight - 1)` class by class, this is the
         same sum with the class loop inside the map."""
-        classes = []
-        if self.pd_person_weight > 1.0:
-            classes += [(rgb, self.pd_person_weight) for rgb in PD_PERSON_RGB.values()]
-        if self.pd_vehicle_weight > 1.0:
-            classes += [(rgb, self.pd_vehicle_weight) for rgb in PD_VEHICLE_RGB.values()]
         wmap = torch.zeros(gt_rgb.shape[0], 1, *latent_hw, dtype=torch.float32, device=gt_rgb.device)
-        for rgb, weight in classes:
+        for rgb, weight in self._pd_classes():
             colour = torch.tensor(rgb, dtype=torch.float32, device=gt_rgb.device) / 127.5 - 1.0
             match = ((gt_rgb - colour[None, :, None, None]).abs().mean(dim=1, keepdim=True) < 0.02).float()
             wmap += F.interpolate(match, tuple(latent_hw), mode="area") * (weight - 1.0)
@@ -416,7 +451,12 @@ class StandardDiffusionLoss(nn.Module):
     def get_loss(self, model_output, target, w, batch):
         """loss.py:163-273: L2 / L1; the ParallelDomain class re-weighting (half of it enters before the focal
         selection, half after); the annealed top-fraction focal loss (keep the `cur_top` largest per-pixel losses of
-        every frame, 0.9 top + 0.1 mean); the EDM weighting."""
+        every frame, 0.9 top + 0.1 mean); the EDM weighting.  Under the `hip` loss engine (set_loss_engine) the same value
+        and its gradient come from gcd_amd/loss_device.py; operands that are not on a GPU then raise GcdError."""
+        if LOSS_ENGINE == "hip":
+            loss = self._get_loss_hip(model_output, target, w, batch)
+            if loss is not None:
+                return loss
         diff = model_output - target
         BT = target.shape[0]
         loss_raw = diff ** 2 if self.loss_type == "l2" else diff.abs()
