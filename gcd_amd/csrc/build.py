@@ -2,9 +2,9 @@
 
 Usage: python -m gcd_amd.csrc.build [--force] [--save-temps]
 The shared objects land next to the package (gcd_amd/libgcd_amd*.so), inside the source tree, and are git-ignored.
-`LIBRARIES` is where a new library is added; `ADDONS`, `EXTENSIONS`, `EXTRAS` and `ADAPTERS` hold the libraries whose
-binding lives in a module of its own (gcd_amd/_lib_clip.py, gcd_amd/_lib_lpips.py, gcd_amd/_lib_loss.py,
-gcd_amd/_lib_lora.py) beside gcd_amd/_lib.py.
+`LIBRARIES` is where a new library is added; `ADDONS`, `EXTENSIONS`, `EXTRAS`, `ADAPTERS` and `DATASETS` hold the libraries
+whose binding lives in a module of its own (gcd_amd/_lib_clip.py, gcd_amd/_lib_lpips.py, gcd_amd/_lib_loss.py,
+gcd_amd/_lib_lora.py, gcd_amd/_lib_pardom.py) beside gcd_amd/_lib.py.
 """
 from __future__ import annotations
 
@@ -87,6 +87,11 @@ ADAPTERS = {lib.name: lib for lib in (
     # LoRA by merged weights: the merge and the projection of dW (gcd_amd/_lib_lora.py, gcd_amd/lora.py)
     Library("gcd_amd_lora", ["lora.hip"], [INCLUDE / "gcd_amd_lora.h"], {}),
 )}
+# ... and after the adapters.
+DATASETS = {lib.name: lib for lib in (
+    # the colours of a ParallelDomain point cloud: class colours and the modal blend (gcd_amd/_lib_pardom.py, gcd_amd/geometry.py)
+    Library("gcd_amd_pardom", ["pardom.hip"], [INCLUDE / "gcd_amd_pardom.h"], {}),
+)}
 MAIN = LIBRARIES["gcd_amd"]
 LIB = MAIN.so
 STAMP = MAIN.stamp
@@ -160,7 +165,8 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True,
     (GCD_TUNE_GEMM_IMPL >= 32).  The product library never contains them."""
     if ablation:
         return _build_ablation(verbose)
-    for lib in (*LIBRARIES.values(), *ADDONS.values(), *EXTENSIONS.values(), *EXTRAS.values(), *ADAPTERS.values()):
+    for lib in (*LIBRARIES.values(), *ADDONS.values(), *EXTENSIONS.values(), *EXTRAS.values(), *ADAPTERS.values(),
+                *DATASETS.values()):
         build_library(lib, force=force, save_temps=save_temps, verbose=verbose)
     return LIB
 

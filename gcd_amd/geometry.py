@@ -5,7 +5,9 @@ from cached point clouds.  This module is that stage: `project_points_to_pixels`
 signatures, shapes and dtypes of the functions they restate, `render_views` is the fused route (one pass over the cloud for
 all cameras of a frame, the filled and resized view stored straight into its slot of a (T, 3, Hp, Wp) batch) and
 `synth_src_dst_rgb` restates the dataset method as a free function.  DESIGN.md §12.2 has the semantics, the accumulation
-scheme and the bars.
+scheme and the bars.  `synth_rgb_pardom` is the ParallelDomain dataset's method: per-frame intrinsics, stored view 16 as the
+re-projection, and in the `segm` modality the colours of `class_colours` (libgcd_amd_pardom.so,
+include/gcd_amd_pardom.h) handed to the same splat.
 
 Two differences in behaviour.  Where no point passes the mask the original raises (a `.max()` of nothing); a kernel
 cannot, so that camera's image is zero, its weights are -1 and `splat` returns the number of visible points per camera
@@ -23,7 +25,7 @@ from typing import Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _lib_pardom
 from .ops import _need_gpu, _stream
 
 _XYZ_CODES = {torch.float16: _lib.RENDER_F16, torch.float32: _lib.RENDER_F32, torch.float64: _lib.RENDER_F64}
@@ -32,10 +34,12 @@ _RGB_CODES[torch.uint8] = _lib.RENDER_U8
 
 
 def pack_cameras(K, RTs, device) -> torch.Tensor:
-    """K (3, 3) and RTs (nc, 4, 4) or (4, 4), any float dtype, host or device -> the (nc, 25) float64 device table
-    the splat reads: K then RT, row-major, each converted to float64 as it is."""
-    K = torch.as_tensor(K).to(torch.float64).reshape(1, 9)
+    """K (3, 3), or (nc, 3, 3) with a matrix per camera, and RTs (nc, 4, 4) or (4, 4), any float dtype, host or device
+    -> the (nc, 25) float64 device table the splat reads: K then RT, row-major, each converted to float64 as it is."""
+    K = torch.as_tensor(K).to(torch.float64).reshape(-1, 9)
     RTs = torch.as_tensor(RTs).to(torch.float64).reshape(-1, 16)
+    if K.shape[0] not in (1, RTs.shape[0]):
+        raise _lib.GcdError(f"pack_cameras: {K.shape[0]} intrinsics for {RTs.shape[0]} cameras")
     return torch.cat([K.to(device).expand(RTs.shape[0], 9), RTs.to(device)], dim=1).contiguous()
 
 
@@ -198,6 +202,144 @@ def synth_src_dst_rgb(pcl_dict, extrinsics_src, extrinsics_dst, avail_intrinsics
             render_views(xyz[4], rgb[4], K, dst[t:t + 1], hw, fhw, spread_radius, reproject_blur, reproject_blur / 4.0,
                          out=[reproject[t]])
     return rgb_src, rgb_dst, reproject
+
+
+# ---- ParallelDomain: class colours and the modal blend ------------------------------------------------------------------
+
+PARDOM_SRC_VIEW = 16           # the stored forward ego viewpoint: what `reproject` renders
+_PARDOM_MODES = {"rgb": _lib_pardom.PARDOM_RGB, "blend": _lib_pardom.PARDOM_BLEND, "palette": _lib_pardom.PARDOM_PALETTE}
+
+
+def semantic_palette(items) -> Tuple[torch.Tensor, int]:
+    """The class colours of an ontology's `items` ({'id': k, 'color': {'r', 'g', 'b'}} each) as the (256, 3) float64
+    table `class_colours` reads, with n_classes = the largest id + 1: row k is (r, g, b) / 255.0 in float64, ids that no
+    item names and the rows from n_classes on are zero.  Host code."""
+    by_id = {int(x["id"]): (x["color"]["r"], x["color"]["g"], x["color"]["b"]) for x in items}
+    if not by_id or min(by_id) < 0 or max(by_id) >= _lib_pardom.PARDOM_PALETTE_ROWS:
+        raise ValueError(f"semantic_palette: class ids must lie in 0 .. {_lib_pardom.PARDOM_PALETTE_ROWS - 1}")
+    table = np.zeros((_lib_pardom.PARDOM_PALETTE_ROWS, 3))
+    for k, v in by_id.items():
+        table[k] = np.array(v) / 255.0
+    return torch.tensor(table), max(by_id) + 1
+
+
+def pardom_frame_mode(t: int, modal_time: int, modality: str):
+    """What frame t of a clip shows: (None, 0.0) for the stored colours as they are (the `rgb` modality: no colour
+    kernel), else (mode of `class_colours`, alpha).  In `segm` the clip fades from colour to class colour over the first
+    modal_time frames."""
+    if modality == "rgb":
+        return None, 0.0
+    if modality != "segm":
+        raise ValueError(f"Unknown selected modality: {modality}")
+    if 0 < t < modal_time:
+        return _lib_pardom.PARDOM_BLEND, t / modal_time
+    if t == 0 and 0 < modal_time:
+        return _lib_pardom.PARDOM_RGB, 0.0
+    return _lib_pardom.PARDOM_PALETTE, 1.0
+
+
+def _points(t: torch.Tensor, channels: int) -> torch.Tensor:
+    """(..., channels) -> (N, channels) with a unit channel stride: a view where the strides allow one."""
+    t = t.reshape(-1, channels)
+    unit = channels == 1 or t.stride(1) == 1
+    return t if t.shape[0] == 0 or (unit and t.stride(0) >= channels) else t.contiguous()
+
+
+def class_colours(ids: Optional[torch.Tensor], rgb: Optional[torch.Tensor], palette: torch.Tensor, alpha: float,
+                  mode: Union[int, str], out: Optional[torch.Tensor] = None, n_classes: int = _lib_pardom.PARDOM_PALETTE_ROWS):
+    """The colours of a cloud's points: ids (N,), (N, 1) or (V, N, 1) uint8 class ids, rgb (N, 3) or (V, N, 3) uint8,
+    palette (256, 3) float64 (see semantic_palette), mode 'rgb' | 'blend' | 'palette' (or the PARDOM_* codes).  `ids` may be
+    None in mode 'rgb' and `rgb` in mode 'palette'.  Returns (out (N, 3) float64 — `out` itself when given, which may
+    have a row stride above 3 — and the number of ids >= n_classes as an int64 device tensor of one element; such a
+    point takes the class colour 0).  Nothing synchronises."""
+    code = _PARDOM_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if code not in _PARDOM_MODES.values():
+        raise ValueError(f"class_colours: mode must be one of {sorted(_PARDOM_MODES)}, got {mode!r}")
+    need_ids, need_rgb = code != _lib_pardom.PARDOM_RGB, code != _lib_pardom.PARDOM_PALETTE
+    given = [t for t, need in ((ids, need_ids), (rgb, need_rgb)) if need or t is not None]
+    if not all(torch.is_tensor(t) for t in (*given, palette)):
+        raise _lib.GcdError("class_colours: the operands must be torch tensors on the GPU; there is no CPU fallback")
+    _need_gpu(*given, palette)
+    if any(t.dtype != torch.uint8 for t in given):
+        raise _lib.GcdError("class_colours: ids and rgb must be uint8")
+    if palette.dtype != torch.float64 or tuple(palette.shape) != (_lib_pardom.PARDOM_PALETTE_ROWS, 3) or not palette.is_contiguous():
+        raise _lib.GcdError(f"class_colours: palette must be a contiguous ({_lib_pardom.PARDOM_PALETTE_ROWS}, 3) float64 tensor")
+    ids = _points(ids, 1) if ids is not None else None
+    rgb = _points(rgb, 3) if rgb is not None else None
+    N = (ids if rgb is None else rgb).shape[0]
+    if ids is not None and rgb is not None and ids.shape[0] != rgb.shape[0]:
+        raise _lib.GcdError(f"class_colours: {ids.shape[0]} ids for {rgb.shape[0]} colours")
+    dev = palette.device
+    if out is None:
+        out = torch.empty(N, 3, dtype=torch.float64, device=dev)
+    else:
+        _need_gpu(out)
+        if out.dtype != torch.float64 or tuple(out.shape) != (N, 3) or (N and (out.stride(1) != 1 or out.stride(0) < 3)):
+            raise _lib.GcdError(f"class_colours: out must be ({N}, 3) float64 with a unit channel stride, got "
+                                f"{tuple(out.shape)} {out.dtype} strides {tuple(out.stride())}")
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    lib = _lib_pardom.load()
+    _lib_pardom.check(lib.gcd_pardom_colours(
+        ids.data_ptr() if ids is not None and N else None, ids.stride(0) if ids is not None and N else 1,
+        rgb.data_ptr() if rgb is not None and N else None, rgb.stride(0) if rgb is not None and N else 3, N,
+        palette.data_ptr(), int(n_classes), float(alpha), code, out.data_ptr() if N else None, out.stride(0) if N else 3,
+        status.data_ptr(), _stream()), "gcd_pardom_colours")
+    return out, status
+
+
+def synth_rgb_pardom(pcl_dict, modality: str, extrinsics, intrinsics, *, palette: Optional[torch.Tensor] = None,
+                     n_classes: int = _lib_pardom.PARDOM_PALETTE_ROWS, modal_time: int = 0, model_frames: int,
+                     render_height: int, render_width: int, frame_height: int, frame_width: int, spread_radius: int,
+                     calc_reproject: bool = False, reproject_rgbd: bool = False):
+    """The ParallelDomain dataset's synth_rgb.  pcl_dict['xyz'][t] (V, N, 3) float16, pcl_dict['rgb'][t] (V, N, 3) uint8
+    and pcl_dict['segm'][t] (V, N, 1) uint8 per frame, on the device; extrinsics (T, 4, 4) and intrinsics (T, 3, 3)
+    float32, the latter normalised to the unit image; palette / n_classes from semantic_palette (the `segm` modality
+    only).  Returns (rgb, reproject or None), (T, 3, Hp, Wp) float32 in [-1, 1] on the device; `reproject`, made when
+    calc_reproject and reproject_rgbd are both set, renders the stored viewpoint 16 alone with a 3 x 3 fill.  An id that
+    is not below n_classes shows the class colour 0 (the original raises an IndexError)."""
+    T = model_frames
+    blur, reproject_blur = 21, 3
+    pardom_frame_mode(0, modal_time, modality)                            # an unknown modality raises before any work
+    K = torch.as_tensor(intrinsics).detach().cpu().to(torch.float32).clone()
+    K[:, 0, :] *= render_width
+    K[:, 1, :] *= render_height
+    old_ar, new_ar = 640.0 / 480.0, render_width / render_height          # the crop of the frame loader, not a stretch
+    if new_ar > old_ar + 1e-3:
+        K[:, 1, 1] = K[:, 0, 0]
+    elif new_ar < old_ar - 1e-3:
+        K[:, 0, 0] = K[:, 1, 1]
+    first = pcl_dict["xyz"][0]
+    if not torch.is_tensor(first):
+        raise _lib.GcdError("synth_rgb_pardom: the clouds must be torch tensors on the GPU; there is no CPU fallback")
+    _need_gpu(first)
+    dev = first.device
+    cams = pack_cameras(K[:T], torch.as_tensor(extrinsics)[:T], dev)      # one copy to the device for the clip
+    shape = (T, 3, frame_height, frame_width)
+    rgb_out = torch.empty(shape, dtype=torch.float32, device=dev)
+    reproject = torch.empty(shape, dtype=torch.float32, device=dev) if calc_reproject and reproject_rgbd else None
+    hw, fhw = (render_height, render_width), (frame_height, frame_width)
+    colours = None
+    if modality == "segm":
+        if palette is None:
+            raise ValueError("synth_rgb_pardom: the segm modality needs a palette (semantic_palette)")
+        palette = palette.to(dev)
+        n_points = max(int(x.shape[0] * x.shape[1]) for x in pcl_dict["xyz"][:T])
+        colours = torch.empty(n_points, 3, dtype=torch.float64, device=dev)      # reused by every frame
+    for t in range(T):
+        xyz, rgb = pcl_dict["xyz"][t], pcl_dict["rgb"][t]
+        V, N = xyz.shape[0], xyz.shape[1]
+        mode, alpha = pardom_frame_mode(t, modal_time, modality)
+        if mode is None:
+            vis = rgb
+        else:
+            vis, _ = class_colours(pcl_dict["segm"][t], rgb, palette, alpha, mode, out=colours[:V * N], n_classes=n_classes)
+            vis = vis.view(V, N, 3)
+        render_views(xyz.reshape(-1, 3), vis.reshape(-1, 3), None, None, hw, fhw, spread_radius, blur, blur / 4.0,
+                     out=[rgb_out[t]], cams=cams[t:t + 1])
+        if reproject is not None:
+            render_views(xyz[PARDOM_SRC_VIEW], vis[PARDOM_SRC_VIEW], None, None, hw, fhw, spread_radius, reproject_blur,
+                         reproject_blur / 4.0, out=[reproject[t]], cams=cams[t:t + 1])
+    return rgb_out, reproject
 
 
 # ---- camera helpers (host, numpy) ---------------------------------------------------------------------------------------
