@@ -1,5 +1,5 @@
 """ctypes binding of libgcd_amd_clip.so (include/gcd_amd_clip.h; gcd_amd/csrc/clip_vision.hip): the kernels of the CLIP ViT
-image tower.  An add-on beside gcd_amd/_lib.py (gcd_amd.csrc.build.ADDONS): the same `Binding` record, made by the same
+image tower.  A library beside gcd_amd/_lib.py (gcd_amd.csrc.build.LIBRARIES): the same `Binding` record, made by the same
 `_bind`, so loading and error reporting behave as for every other library — a missing shared object or a non-zero status
 raises GcdError, nothing falls back."""
 from __future__ import annotations

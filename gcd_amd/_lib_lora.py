@@ -1,5 +1,5 @@
 """ctypes binding of libgcd_amd_lora.so (include/gcd_amd_lora.h; gcd_amd/csrc/lora.hip): LoRA by merged weights.
-A library beside gcd_amd/_lib.py (gcd_amd.csrc.build.ADAPTERS), like gcd_amd/_lib_loss.py: the same `Binding` record, made
+A library beside gcd_amd/_lib.py (gcd_amd.csrc.build.LIBRARIES), like gcd_amd/_lib_loss.py: the same `Binding` record, made
 by the same `_bind`, so loading and error reporting behave as for every other library — a missing shared object or a
 non-zero status raises GcdError, nothing falls back."""
 from __future__ import annotations

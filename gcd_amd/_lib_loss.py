@@ -1,5 +1,5 @@
 """ctypes binding of libgcd_amd_loss.so (include/gcd_amd_loss.h; gcd_amd/csrc/loss.hip): the fine-tune loss on the device.
-A library beside gcd_amd/_lib.py (gcd_amd.csrc.build.EXTRAS), like gcd_amd/_lib_lpips.py: the same `Binding` record, made
+A library beside gcd_amd/_lib.py (gcd_amd.csrc.build.LIBRARIES), like gcd_amd/_lib_lpips.py: the same `Binding` record, made
 by the same `_bind`, so loading and error reporting behave as for every other library — a missing shared object or a
 non-zero status raises GcdError, nothing falls back."""
 from __future__ import annotations

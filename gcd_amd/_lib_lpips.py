@@ -1,5 +1,5 @@
 """ctypes binding of libgcd_amd_lpips.so (include/gcd_amd_lpips.h; gcd_amd/csrc/lpips.hip): the kernels of the LPIPS metric.
-A library beside gcd_amd/_lib.py (gcd_amd.csrc.build.EXTENSIONS), like gcd_amd/_lib_clip.py: the same `Binding` record,
+A library beside gcd_amd/_lib.py (gcd_amd.csrc.build.LIBRARIES), like gcd_amd/_lib_clip.py: the same `Binding` record,
 made by the same `_bind`, so loading and error reporting behave as for every other library — a missing shared object or
 a non-zero status raises GcdError, nothing falls back."""
 from __future__ import annotations

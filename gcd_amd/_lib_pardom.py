@@ -1,5 +1,5 @@
 """ctypes binding of libgcd_amd_pardom.so (include/gcd_amd_pardom.h; gcd_amd/csrc/pardom.hip): the colours of a
-ParallelDomain point cloud.  A library beside gcd_amd/_lib.py (gcd_amd.csrc.build.DATASETS), like gcd_amd/_lib_lora.py: the
+ParallelDomain point cloud.  A library beside gcd_amd/_lib.py (gcd_amd.csrc.build.LIBRARIES), like gcd_amd/_lib_lora.py: the
 same `Binding` record, made by the same `_bind`, so loading and error reporting behave as for every other library — a
 missing shared object or a non-zero status raises GcdError, nothing falls back."""
 from __future__ import annotations

@@ -2,9 +2,9 @@
 
 Usage: python -m gcd_amd.csrc.build [--force] [--save-temps]
 The shared objects land next to the package (gcd_amd/libgcd_amd*.so), inside the source tree, and are git-ignored.
-`LIBRARIES` is where a new library is added; `ADDONS`, `EXTENSIONS`, `EXTRAS`, `ADAPTERS` and `DATASETS` hold the libraries
-whose binding lives in a module of its own (gcd_amd/_lib_clip.py, gcd_amd/_lib_lpips.py, gcd_amd/_lib_loss.py,
-gcd_amd/_lib_lora.py, gcd_amd/_lib_pardom.py) beside gcd_amd/_lib.py.
+`LIBRARIES` is where a new library is added; the first five are bound by gcd_amd/_lib.py, each later one by a module of
+its own beside it (gcd_amd/_lib_clip.py, gcd_amd/_lib_lpips.py, gcd_amd/_lib_loss.py, gcd_amd/_lib_lora.py,
+gcd_amd/_lib_pardom.py).
 """
 from __future__ import annotations
 
@@ -53,7 +53,8 @@ class Library(NamedTuple):
 
 # Only the first entry is part of `sources_digest()`: no source of the others can change a kernel that a sampler step
 # launches (the Euler step that the traffic profile describes never launches the stage kernel either; the metrics and the
-# renderer produce and judge the data of a step and launch nothing inside one).
+# renderer produce and judge the data of a step and launch nothing inside one, and so do the conditioner's image tower,
+# LPIPS, the loss, the adapters and the ParallelDomain colours).
 LIBRARIES = {lib.name: lib for lib in (
     Library("gcd_amd", SOURCES, HEADERS, EXTRA_FLAGS),
     # kernels of the fine-tune step only
@@ -66,29 +67,14 @@ LIBRARIES = {lib.name: lib for lib in (
     Library("gcd_amd_metrics", ["metrics.hip"], [INCLUDE / "gcd_amd_metrics.h"], {}),
     # point clouds to (source, target) frames
     Library("gcd_amd_render", ["render.hip"], [INCLUDE / "gcd_amd_render.h"], {}),
-)}
-# Libraries bound outside gcd_amd/_lib.py, built by build() after LIBRARIES with the same stamp mechanism.
-ADDONS = {lib.name: lib for lib in (
     # the CLIP ViT image tower's own kernels (gcd_amd/_lib_clip.py, gcd_amd/clip_vision.py)
     Library("gcd_amd_clip", ["clip_vision.hip"], [INCLUDE / "gcd_amd_clip.h"], {}),
-)}
-# The same for the libraries that came after the image tower (each again with a binding module of its own).
-EXTENSIONS = {lib.name: lib for lib in (
     # the LPIPS metric's own kernels (gcd_amd/_lib_lpips.py, gcd_amd/lpips.py)
     Library("gcd_amd_lpips", ["lpips.hip"], [INCLUDE / "gcd_amd_lpips.h"], {}),
-)}
-# ... and after the perceptual metric.
-EXTRAS = {lib.name: lib for lib in (
     # the fine-tune loss on the device (gcd_amd/_lib_loss.py, gcd_amd/loss_device.py)
     Library("gcd_amd_loss", ["loss.hip"], [INCLUDE / "gcd_amd_loss.h"], {}),
-)}
-# ... and after the loss.
-ADAPTERS = {lib.name: lib for lib in (
     # LoRA by merged weights: the merge and the projection of dW (gcd_amd/_lib_lora.py, gcd_amd/lora.py)
     Library("gcd_amd_lora", ["lora.hip"], [INCLUDE / "gcd_amd_lora.h"], {}),
-)}
-# ... and after the adapters.
-DATASETS = {lib.name: lib for lib in (
     # the colours of a ParallelDomain point cloud: class colours and the modal blend (gcd_amd/_lib_pardom.py, gcd_amd/geometry.py)
     Library("gcd_amd_pardom", ["pardom.hip"], [INCLUDE / "gcd_amd_pardom.h"], {}),
 )}
@@ -165,8 +151,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True,
     (GCD_TUNE_GEMM_IMPL >= 32).  The product library never contains them."""
     if ablation:
         return _build_ablation(verbose)
-    for lib in (*LIBRARIES.values(), *ADDONS.values(), *EXTENSIONS.values(), *EXTRAS.values(), *ADAPTERS.values(),
-                *DATASETS.values()):
+    for lib in LIBRARIES.values():
         build_library(lib, force=force, save_temps=save_temps, verbose=verbose)
     return LIB
 

@@ -3,7 +3,7 @@
  * matrix, the token assembly with ln_pre, self-attention at head dim 80 and the bias + erf-GELU between c_fc and c_proj.
  * The GEMMs and the other LayerNorms of the tower are gcd_gemm_f16 / gcd_layernorm_f16 of libgcd_amd.so.
  *
- * A library of its own (an add-on: gcd_amd/csrc/build.py ADDONS, gcd_amd/_lib_clip.py): include/gcd_amd.h and its ABI
+ * A library of its own (gcd_amd/csrc/build.py LIBRARIES, gcd_amd/_lib_clip.py): include/gcd_amd.h and its ABI
  * version do not change.  Same rules as gcd_amd.h: raw device pointers, the caller's hipStream_t, no allocation, no
  * synchronisation, no atomics; every argument is checked before anything is launched, and a non-zero status comes with
  * a message in gcd_clip_last_error().  Every payload element of every output is stored by every call. */

@@ -4,7 +4,7 @@
  *   dB = scale * dW A^T        dA = scale * B^T dW
  * with A [r, K], B [N, r], W0 / W / dW [N, K], all fp32, row-major and contiguous.
  *
- * A library of its own (gcd_amd/csrc/build.py ADAPTERS, gcd_amd/_lib_lora.py): include/gcd_amd.h and its ABI version do
+ * A library of its own (gcd_amd/csrc/build.py LIBRARIES, gcd_amd/_lib_lora.py): include/gcd_amd.h and its ABI version do
  * not change.  Same rules as gcd_amd.h: raw device pointers, the caller's hipStream_t, no allocation, no synchronisation;
  * every host argument is checked before anything is launched, and a non-zero status comes with a message in
  * gcd_lora_last_error().  Both entry points are GROUPED: one call covers every adapted layer through a table of

@@ -2,7 +2,7 @@
  * (gcd_amd/loss_device.py; the `hip` loss engine of gcd_amd/training.py): the ParallelDomain class weight map, the
  * annealed top-fraction focal loss with the EDM weighting, and its gradient with respect to the model output.
  *
- * A library of its own (gcd_amd/csrc/build.py EXTRAS, gcd_amd/_lib_loss.py): include/gcd_amd.h and its ABI version do not
+ * A library of its own (gcd_amd/csrc/build.py LIBRARIES, gcd_amd/_lib_loss.py): include/gcd_amd.h and its ABI version do not
  * change.  Same rules as gcd_amd.h: raw device pointers, the caller's hipStream_t, no allocation, no synchronisation;
  * every argument is checked before anything is launched, and a non-zero status comes with a message in
  * gcd_loss_last_error().  Every payload element of every output is stored by every call.  There is no floating-point

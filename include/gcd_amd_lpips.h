@@ -3,7 +3,7 @@
  * of the images, ReLU with the 2x2 max-pool of VGG-16, and the normalised squared feature distance of one tap with its
  * 1x1 `lin` weights.  The 13 convolutions of the tower are gcd_gemm_f16 (GCD_GEMM_CONV3X3, fp16 output, bias).
  *
- * A library of its own (gcd_amd/csrc/build.py EXTENSIONS, gcd_amd/_lib_lpips.py): include/gcd_amd.h and its ABI version
+ * A library of its own (gcd_amd/csrc/build.py LIBRARIES, gcd_amd/_lib_lpips.py): include/gcd_amd.h and its ABI version
  * do not change.  Same rules as gcd_amd.h: raw device pointers, the caller's hipStream_t, no allocation, no
  * synchronisation, no atomics; every argument is checked before anything is launched, and a non-zero status comes with
  * a message in gcd_lpips_last_error().  Every payload element of every (non-null) output is stored by every call. */

@@ -2,7 +2,7 @@
  * (gcd_amd/geometry.py class_colours, synth_rgb_pardom): a point's colour is its stored RGB, the colour of its semantic
  * class, or a blend of the two, written as float64 for the splat of include/gcd_amd_render.h to read.
  *
- * A library of its own (gcd_amd/csrc/build.py DATASETS, gcd_amd/_lib_pardom.py): include/gcd_amd_render.h and its ABI
+ * A library of its own (gcd_amd/csrc/build.py LIBRARIES, gcd_amd/_lib_pardom.py): include/gcd_amd_render.h and its ABI
  * version do not change.  Same rules as gcd_amd.h: raw device pointers, the caller's hipStream_t, no allocation, no
  * synchronisation; every argument is checked before anything is launched, and a non-zero status comes with a message in
  * gcd_pardom_last_error().  Every payload element of `out` and the counter are stored by every call; the only atomic is

@@ -1,27 +1,22 @@
-"""CPU: LoRA by merged weights (gcd_amd/lora.py) and its library (libgcd_amd_lora.so; gcd_amd.csrc.build.ADAPTERS,
+"""CPU: LoRA by merged weights (gcd_amd/lora.py) and its library (libgcd_amd_lora.so; gcd_amd.csrc.build.LIBRARIES,
 gcd_amd/_lib_lora.py).  The layer selection is the reference's: tests/golden/lora_layers.json was written by
-tools/make_golden_lora.py from the reference's own VideoUNet.  The library is held to the rules
-tests/test_loss_device_host.py states for its own: header, binding table and exports are one set, one ABI version, the
-limits mirrored, no shared source, header or symbol, a build from a clean tree through build() — and, because this one has
-a table entry, the ctypes mirror has the layout gcc gives the C struct."""
+tools/make_golden_lora.py from the reference's own VideoUNet.  The library's limits fit the adapted layers, its table entry
+mirrors every member of the C struct, and it refuses bad arguments (the rules every library is held to, the entry's layout
+under gcc among them, are tests/test_libraries_host.py's)."""
 import ctypes
-import importlib.util
 import json
 import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import pytest
 import torch
 
-from gcd_amd import _lib, _lib_clip, _lib_lora, _lib_loss, _lib_lpips, lora as L
+from gcd_amd import _lib_lora, lora as L
 from gcd_amd._lib import GcdError
 from gcd_amd.csrc import build as b
 from oracle import svd_unet_ref as O
-from test_libraries_host import DECL, ROOT, _dynamic_exports, _public_headers
 
-NAME = "gcd_amd_lora"
+ROOT = Path(__file__).resolve().parent.parent
 GOLD = json.loads((Path(__file__).resolve().parent / "golden" / "lora_layers.json").read_text())
 CONFIGS = {"TINY": O.TINY, "KUBRIC": O.KUBRIC}
 
@@ -158,116 +153,21 @@ def test_reference_state_dict_names_round_trip():
 
 
 # ----------------------------------------------------------------------------------------------------------- the library
-def test_adapters_table_and_binding_name_the_same_library():
-    assert list(b.ADAPTERS) == [NAME] and NAME not in _lib.BINDINGS
-    assert not any(NAME in table for table in (b.LIBRARIES, b.ADDONS, b.EXTENSIONS, b.EXTRAS))
-    lib, rec = b.ADAPTERS[NAME], _lib_lora.BINDING
-    assert isinstance(lib, b.Library) and isinstance(rec, _lib.Binding) and rec.name == NAME
-    assert lib.so == rec.path == ROOT / "gcd_amd" / f"lib{NAME}.so" and lib.stamp == ROOT / "gcd_amd" / f".lib{NAME}.stamp"
-    assert (_lib_lora.load, _lib_lora.check) == (rec.load, rec.check)
-    assert lib.stamp.name in (ROOT / ".gitignore").read_text().split()
-
-
-def test_header_binding_table_and_exports_are_one_set():
-    b.build(verbose=False)
-    lib, rec = b.ADAPTERS[NAME], _lib_lora.BINDING
-    headers = _public_headers(lib)
-    assert len(headers) == len(rec.tables) == 1
-    declared = set(re.findall(DECL, headers[0].read_text(), flags=re.M))
-    assert declared == set(rec.tables[0]), declared ^ set(rec.tables[0])
-    assert {rec.version_entry, rec.error_entry} <= declared
-    exported = {n for n in _dynamic_exports(lib.so) if n.startswith("gcd_")}
-    assert exported == declared, exported ^ declared
-    assert len(declared) == 5
-
-
-def test_header_binding_and_library_agree_on_the_abi_version_and_limits():
-    b.build(verbose=False)
-    lib, rec = b.ADAPTERS[NAME], _lib_lora.BINDING
-    text = _public_headers(lib)[0].read_text()
-    assert [int(v) for v in re.findall(r"^#define GCD_AMD_\w*ABI_VERSION (\d+)", text, flags=re.M)] == [1]
-    assert rec.abi_version == _lib_lora.LORA_ABI_VERSION == 1
-    assert getattr(rec.load(), rec.version_entry)() == 1
-    mirrored = {"GCD_LORA_MAX_RANK": _lib_lora.LORA_MAX_RANK, "GCD_LORA_MAX_ENTRIES": _lib_lora.LORA_MAX_ENTRIES,
-                "GCD_LORA_MAX_DIM": _lib_lora.LORA_MAX_DIM, "GCD_LORA_MERGE_TILE": _lib_lora.LORA_MERGE_TILE,
-                "GCD_LORA_PROJECT_TILE": _lib_lora.LORA_PROJECT_TILE}
-    defines = dict(re.findall(r"^#define (GCD_LORA_\w+) (\d+)", text, flags=re.M))
-    assert {k: int(v) for k, v in defines.items()} == mirrored          # every define of the header, and nothing else
-    assert {n for n in vars(_lib_lora) if n.startswith("LORA_") and n.isupper()} == \
-        {k[4:] for k in mirrored} | {"LORA_LIB_PATH", "LORA_ABI_VERSION", "LORA_SIGNATURES"}
+def test_limits_fit_the_adapted_layers():
     assert _lib_lora.LORA_MAX_RANK == 64 and _lib_lora.LORA_MAX_ENTRIES >= 248
     assert _lib_lora.LORA_MAX_DIM >= max(max(N, K) for _, N, K in GOLD["KUBRIC"]["time_lora"])
 
 
-def test_library_shares_no_symbol_source_or_header():
-    lib, rec = b.ADAPTERS[NAME], _lib_lora.BINDING
-    for other in (*_lib.BINDINGS.values(), _lib_clip.BINDING, _lib_lpips.BINDING, _lib_loss.BINDING):
-        for t in other.tables:
-            assert not set(t) & set(rec.tables[0]), (other.name, set(t) & set(rec.tables[0]))
-    for other in (*b.LIBRARIES.values(), *b.ADDONS.values(), *b.EXTENSIONS.values(), *b.EXTRAS.values()):
-        assert not set(lib.sources) & set(other.sources) and not set(lib.headers) & set(other.headers), other.name
-    assert all((b.CSRC / s).is_file() for s in lib.sources) and all(h.is_file() for h in lib.headers)
-    for s in lib.sources:       # the source includes its own public header and nothing else of the project
-        includes = re.findall(r'^#include "([^"]+)"', (b.CSRC / s).read_text(), flags=re.M)
-        assert includes == ["../../include/gcd_amd_lora.h"], includes
-    assert not set(lib.sources) & set(b.SOURCES) and not set(lib.headers) & set(b.HEADERS)      # not in the step's digest
-    structs = [n for n, v in vars(_lib_lora).items()
-               if isinstance(v, type) and issubclass(v, ctypes.Structure) and v.__module__ == _lib_lora.__name__]
-    assert structs == ["LoraEntry"]
-    assert re.search(r"^\} gcd_lora_entry;", _public_headers(lib)[0].read_text(), flags=re.M)
-
-
-def test_entry_layout_matches_header(tmp_path):
-    """The ctypes mirror has the C struct's field offsets and size (checked with gcc)."""
-    assert shutil.which("gcc"), "gcc is a prerequisite of the suite"
+def test_entry_mirrors_every_member_of_the_struct():
+    """(Offsets and size against gcc: tests/test_libraries_host.py test_struct_layout_matches_header[LoraEntry].)"""
     cls = _lib_lora.LoraEntry
     fields = [f[0] for f in cls._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT / "include" / "gcd_amd_lora.h"}"', 'int main(void) {']
-    src += [f'  printf("{n} %zu\\n", offsetof(gcd_lora_entry, {n}));' for n in fields]
-    src += ['  printf("sizeof %zu\\n", sizeof(gcd_lora_entry));', '  return 0;', '}']
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c11", "-o", str(exe), str(c)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    for n in fields:
-        assert int(out[n]) == getattr(cls, n).offset, n
-    assert int(out["sizeof"]) == ctypes.sizeof(cls) == 88
+    assert ctypes.sizeof(cls) == 88
     # every member of the C struct is mirrored (names between the braces of the typedef)
     body = re.search(r"typedef struct \{(.*?)\} gcd_lora_entry;", (ROOT / "include" / "gcd_amd_lora.h").read_text(), flags=re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     members = [n for decl in body.split(";") if decl.strip() for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
     assert members == fields, (members, fields)
-
-
-def test_library_builds_from_a_clean_tree_through_build(tmp_path):
-    """A copy of the build script, the sources and the headers, and nothing built.  With every other library current,
-    build() compiles exactly this one and returns the main library's path; a second call compiles nothing."""
-    shutil.copytree(ROOT / "gcd_amd" / "csrc", tmp_path / "gcd_amd" / "csrc", ignore=shutil.ignore_patterns("build", "__pycache__"))
-    shutil.copytree(ROOT / "include", tmp_path / "include")
-    spec = importlib.util.spec_from_file_location("clean_tree_build_lora", tmp_path / "gcd_amd" / "csrc" / "build.py")
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    lib = m.ADAPTERS[NAME]
-    assert lib.so == tmp_path / "gcd_amd" / f"lib{NAME}.so" and not lib.so.exists()
-    others = (*m.LIBRARIES.values(), *m.ADDONS.values(), *m.EXTENSIONS.values(), *m.EXTRAS.values())
-    for o in others:
-        o.so.write_bytes(b"")
-        o.stamp.write_text(m._digest(o))
-    for f in ("engine.py", "ops.py", "sampling.py"):            # (the host side that sources_digest() reads)
-        shutil.copy(ROOT / "gcd_amd" / f, tmp_path / "gcd_amd" / f)
-    digest = m.sources_digest()
-    assert m.build(verbose=False) == m.LIB == tmp_path / "gcd_amd" / "libgcd_amd.so"
-    assert all(o.so.stat().st_size == 0 for o in others)
-    assert lib.stamp.read_text() == m._digest(lib)
-    exported = {n for n in _dynamic_exports(lib.so) if n.startswith("gcd_")}
-    assert exported == set(_lib_lora.LORA_SIGNATURES), exported
-    before = lib.so.stat().st_mtime_ns
-    m.build(verbose=False)
-    assert lib.so.stat().st_mtime_ns == before
-    # the adapters are no part of what a sampler step launches: their source does not move sources_digest()
-    (tmp_path / "gcd_amd" / "csrc" / "lora.hip").write_text("// changed\n")
-    assert m._digest(lib) != lib.stamp.read_text() and m.sources_digest() == digest
 
 
 def test_bad_arguments_return_a_status_and_a_message():

@@ -1,25 +1,16 @@
-"""CPU: the LPIPS drop-in (gcd_amd/lpips.py) and its library (libgcd_amd_lpips.so; gcd_amd.csrc.build.EXTENSIONS,
+"""CPU: the LPIPS drop-in (gcd_amd/lpips.py) and its library (libgcd_amd_lpips.so; gcd_amd.csrc.build.LIBRARIES,
 gcd_amd/_lib_lpips.py).  The oracle of the GPU tests (tests/lpips_util.py) is pinned to the executed reference recorded
 in tests/golden/lpips_tiny.pt; the module has the reference's 33 names and loads the way the reference does; operands
-that the HIP path cannot take raise GcdError; and the library is held to the rules tests/test_clip_library_host.py states
-for an add-on: header, binding table and exports are one set, one ABI version, no shared source, header or symbol, no
-ctypes.Structure, the limits mirrored, and a build from a clean tree through build()."""
-import ctypes
-import importlib.util
-import re
-import shutil
-
+that the HIP path cannot take raise GcdError; and the library's limits fit the tower (the rules every library is held to
+are tests/test_libraries_host.py's)."""
 import pytest
 import torch
 
 import lpips_util as U
-from gcd_amd import _lib, _lib_clip, _lib_lpips
+from gcd_amd import _lib_lpips
 from gcd_amd._lib import GcdError
-from gcd_amd.csrc import build as b
 from gcd_amd.lpips import LPIPS
-from test_libraries_host import DECL, ROOT, _dynamic_exports, _public_headers
 
-NAME = "gcd_amd_lpips"
 CASES = ("tiny_40x56", "tiny_37x51", "full_64x96")
 
 
@@ -135,79 +126,5 @@ def test_training_loss_type_lpips_keeps_raising():
 
 
 # ----------------------------------------------------------------------------------------------------------- the library
-def test_extension_table_and_binding_name_the_same_library():
-    assert list(b.EXTENSIONS) == [NAME] and NAME not in b.LIBRARIES and NAME not in b.ADDONS and NAME not in _lib.BINDINGS
-    lib, rec = b.EXTENSIONS[NAME], _lib_lpips.BINDING
-    assert isinstance(lib, b.Library) and isinstance(rec, _lib.Binding) and rec.name == NAME
-    assert lib.so == rec.path == ROOT / "gcd_amd" / f"lib{NAME}.so" and lib.stamp == ROOT / "gcd_amd" / f".lib{NAME}.stamp"
-    assert (_lib_lpips.load, _lib_lpips.check) == (rec.load, rec.check)
-    assert lib.stamp.name in (ROOT / ".gitignore").read_text().split()
-
-
-def test_header_binding_table_and_exports_are_one_set():
-    b.build(verbose=False)
-    lib, rec = b.EXTENSIONS[NAME], _lib_lpips.BINDING
-    headers = _public_headers(lib)
-    assert len(headers) == len(rec.tables) == 1
-    declared = set(re.findall(DECL, headers[0].read_text(), flags=re.M))
-    assert declared == set(rec.tables[0]), declared ^ set(rec.tables[0])
-    assert {rec.version_entry, rec.error_entry} <= declared
-    exported = {n for n in _dynamic_exports(lib.so) if n.startswith("gcd_")}
-    assert exported == declared, exported ^ declared
-    assert len(declared) == 5
-
-
-def test_header_binding_and_library_agree_on_the_abi_version_and_limits():
-    b.build(verbose=False)
-    lib, rec = b.EXTENSIONS[NAME], _lib_lpips.BINDING
-    text = _public_headers(lib)[0].read_text()
-    assert [int(v) for v in re.findall(r"^#define GCD_AMD_\w*ABI_VERSION (\d+)", text, flags=re.M)] == [1]
-    assert rec.abi_version == _lib_lpips.LPIPS_ABI_VERSION == 1
-    assert getattr(rec.load(), rec.version_entry)() == 1
-    mirrored = {"GCD_LPIPS_MAX_C": _lib_lpips.LPIPS_MAX_C, "GCD_LPIPS_C_MULTIPLE": _lib_lpips.LPIPS_C_MULTIPLE,
-                "GCD_LPIPS_MAX_BLOCKS": _lib_lpips.LPIPS_MAX_BLOCKS, "GCD_LPIPS_MAX_TAPS": _lib_lpips.LPIPS_MAX_TAPS,
-                "GCD_LPIPS_MAX_IMAGES": _lib_lpips.LPIPS_MAX_IMAGES, "GCD_LPIPS_IMAGE_CHANNELS": _lib_lpips.LPIPS_IMAGE_CHANNELS}
-    defines = dict(re.findall(r"^#define (GCD_LPIPS_\w+) (\d+)", text, flags=re.M))
-    assert {k: int(v) for k, v in defines.items()} == mirrored          # every limit of the header, and nothing else
+def test_limits_fit_the_vgg16_tower():
     assert _lib_lpips.LPIPS_MAX_C >= 512 and _lib_lpips.LPIPS_MAX_C % _lib_lpips.LPIPS_C_MULTIPLE == 0
-
-
-def test_extension_shares_no_symbol_source_or_header_and_has_no_structure():
-    lib, rec = b.EXTENSIONS[NAME], _lib_lpips.BINDING
-    for other in (*_lib.BINDINGS.values(), _lib_clip.BINDING):
-        for t in other.tables:
-            assert not set(t) & set(rec.tables[0]), (other.name, set(t) & set(rec.tables[0]))
-    for other in (*b.LIBRARIES.values(), *b.ADDONS.values()):
-        assert not set(lib.sources) & set(other.sources) and not set(lib.headers) & set(other.headers), other.name
-    assert all((b.CSRC / s).is_file() for s in lib.sources) and all(h.is_file() for h in lib.headers)
-    for s in lib.sources:       # the source includes its own public header and nothing else of the project
-        includes = re.findall(r'^#include "([^"]+)"', (b.CSRC / s).read_text(), flags=re.M)
-        assert includes == ["../../include/gcd_amd_lpips.h"], includes
-    assert not [n for n, v in vars(_lib_lpips).items()
-                if isinstance(v, type) and issubclass(v, ctypes.Structure) and v.__module__ == _lib_lpips.__name__]
-    assert "struct" not in re.sub(r"/\*.*?\*/", "", _public_headers(lib)[0].read_text(), flags=re.S)
-    assert not set(lib.sources) & set(b.SOURCES) and not set(lib.headers) & set(b.HEADERS)      # not in the step's digest
-
-
-def test_extension_builds_from_a_clean_tree_through_build(tmp_path):
-    """A copy of the build script, the sources and the headers, and nothing built.  With every other library current,
-    build() compiles exactly this one and returns the main library's path; a second call compiles nothing."""
-    shutil.copytree(ROOT / "gcd_amd" / "csrc", tmp_path / "gcd_amd" / "csrc", ignore=shutil.ignore_patterns("build", "__pycache__"))
-    shutil.copytree(ROOT / "include", tmp_path / "include")
-    spec = importlib.util.spec_from_file_location("clean_tree_build_lpips", tmp_path / "gcd_amd" / "csrc" / "build.py")
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    lib = m.EXTENSIONS[NAME]
-    assert lib.so == tmp_path / "gcd_amd" / f"lib{NAME}.so" and not lib.so.exists()
-    others = (*m.LIBRARIES.values(), *m.ADDONS.values())
-    for o in others:
-        o.so.write_bytes(b"")
-        o.stamp.write_text(m._digest(o))
-    assert m.build(verbose=False) == m.LIB == tmp_path / "gcd_amd" / "libgcd_amd.so"
-    assert all(o.so.stat().st_size == 0 for o in others)
-    assert lib.stamp.read_text() == m._digest(lib)
-    exported = {n for n in _dynamic_exports(lib.so) if n.startswith("gcd_")}
-    assert exported == set(_lib_lpips.LPIPS_SIGNATURES), exported
-    before = lib.so.stat().st_mtime_ns
-    m.build(verbose=False)
-    assert lib.so.stat().st_mtime_ns == before
