@@ -15,6 +15,9 @@ plugin surface.  YAML `target:` strings that pointed at `sgm.modules.diffusionmo
     first-stage decoder_config   gcd_amd.temporal_ae.VideoDecoder
     loss_fn_config.target        gcd_amd.training.StandardDiffusionLoss          (fine-tune step, a vertical slice)
 
+The object that owns them: gcd_amd.diffusion.DiffusionEngine (the reference's engine without Lightning), built from GCD's
+own YAML by gcd_amd.config (`sgm.*` targets translated), run by `python -m gcd_amd.infer` / gcd_amd.inference.
+
 Beside the sockets: gcd_amd.parallel (clip sharding over GPUs), gcd_amd.camera (pose trajectories),
 gcd_amd.metrics (PSNR / SSIM of the evaluation script), gcd_amd.eval_io (its frame / video writer), gcd_amd.autograd_ops (HIP-backed autograd operators).
 
